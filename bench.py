@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s (+ achieved HBM GB/s) of the quantized decode hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload int4_b1|int8_b1|int4_b32_u4kv]
+    python bench.py --gpus N --steps K --warmup W [--workload int4_b1|int8_b1|int4_b32_u4kv] [--full] [--dump-outputs DIR]
 
 A "step" is one decode step of Qwen2-7B (synthetic InstantQuant weights, synthetic KV history of
 2048 tokens) over one batch; at N > 1 the model is tensor-parallel over N ranks (one process per
 GPU, RCCL all-reduce over xGMI) -- total work is fixed, so scaling is "strong".  W warm-up graph
 replays, then exactly K replays are timed between barrier + synchronize on both sides; the maximum
 over ranks is used; rank 0 prints ONE JSON line.
+
+A plain run does only that, on the path `value` comes from (its warm-up ends with one untimed pass of
+min(K, 256) steps, so that its one timed block is not a cold first one).  --full adds everything else the record
+holds: the other runner's figures, per-kernel breakdown and roofline, CPU baselines, the secondary
+workloads, and the median of 5 such K-step blocks.  --dump-outputs DIR writes what the timed path
+computed in its last step (logits, next token ids) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.
 
 Default workload: the configuration BASELINE.json's metric and target are quoted on -- Qwen2-7B int4
 (group 128) weight-only, bf16 KV, batch 1, seq 2048 (first row).
@@ -242,6 +249,12 @@ def timed_blocks(run_n, steps, blocks, world=1, device=None, sync=None, before_b
     return srt[len(srt) // 2], times
 
 
+def settle_steps(args):
+    """Warm-up steps a plain run adds after --warmup, rewound like a block and untimed: its ONE timed block is then not the slow
+    first block that --full's median of 5 leaves out.  A fixed count: the dumped outputs stay the same from run to run."""
+    return 0 if args.full else min(args.steps, 256)
+
+
 def blocks_summary(times, steps):
     srt = sorted(times)
     return {"count": len(times), "steps_each": steps, "ms_per_step_median": round(srt[len(srt) // 2] / steps * 1e3, 4),
@@ -249,7 +262,7 @@ def blocks_summary(times, steps):
             "spread": round((srt[-1] - srt[0]) / srt[len(srt) // 2], 4)}
 
 
-def host_runner_bench(args, torch, decoder, ops, model, sess, batch, max_len, kv_mode, fuse, graph, steps, blocks):
+def host_runner_bench(args, torch, decoder, ops, model, sess, batch, max_len, kv_mode, fuse, graph, steps, blocks, outputs=None):
     """The SAME decode step through the C++ operator layer (dash-infer_amd/host): the reference's Qwen2 operator list
     (dash-infer_amd/ref_graph.py: qwen_v15.py:187-388; the MoE layers of qwen_v20_moe.py:318-391 for cfg5_moe) -> fusion pass (host/fusion_pass.cpp; fuse=False: the list as it is, fourteen launches
     per layer) -> OpFactory -> HipModelRunner (host/model_runner.cpp: Alloc -> Forward per operator per step, model.cpp:1248-1325),
@@ -278,6 +291,9 @@ def host_runner_bench(args, torch, decoder, ops, model, sess, batch, max_len, kv
                 vs = [[int(p) for p in sess.kv[li].v_host[b].tolist()] for li in range(len(model.layers))]
                 m.request_adopt(SEQ_LEN, ids[b], ks, vs)
             m.decode_steps(max(2, args.warmup), graph=graph)
+            if settle_steps(args):
+                m.requests_rewind(SEQ_LEN)
+                m.decode_steps(settle_steps(args), graph=graph)
             m.sync_ids()
 
             def run_n(n):
@@ -285,6 +301,8 @@ def host_runner_bench(args, torch, decoder, ops, model, sess, batch, max_len, kv
 
             med, times = timed_blocks(run_n, steps, blocks, sync=stream.synchronize, before_block=lambda: m.requests_rewind(SEQ_LEN))
             last = m.sync_ids()
+            if outputs is not None:   # --dump-outputs: the last timed step's logits and next ids, copied before the model is closed
+                outputs.update(logits=model_tensor(m, "logits"), next_ids=last)
         finally:
             m.close()
     return {"tokens_per_s": round(batch * steps / med, 2), "ms_per_step": round(med / steps * 1e3, 4), "blocks": blocks_summary(times, steps),
@@ -292,7 +310,8 @@ def host_runner_bench(args, torch, decoder, ops, model, sess, batch, max_len, kv
             "why_unfused": rep["why"] if not rep["fused"] else None, "last_ids": last[:4]}
 
 
-def host_runner_bench_tp(args, torch, decoder, ops, cfg, spec, sess, comm, batch, max_len, kv_mode, rank, world, local_rank, steps, blocks):
+def host_runner_bench_tp(args, torch, decoder, ops, cfg, spec, sess, comm, batch, max_len, kv_mode, rank, world, local_rank, steps, blocks,
+                         outputs=None):
     """N > 1: the decode step through the C++ operator layer on every rank -- one HipModelRunner per rank PROCESS over
     its tp.py weight slices (the reference-shaped K-split lm_head: Gemm(splitk) + AllReduce, model_base.py:690-703), the reference's
     operator list with its AllReduce operators -> fusion pass -> OpFactory(HIP), HIPContext carrying the rank's RCCL communicator (and
@@ -340,6 +359,9 @@ def host_runner_bench_tp(args, torch, decoder, ops, cfg, spec, sess, comm, batch
     try:
         with torch.cuda.stream(stream):
             m.decode_steps(max(2, args.warmup), graph=True)
+            if settle_steps(args):
+                m.requests_rewind(SEQ_LEN)
+                m.decode_steps(settle_steps(args), graph=True)
             m.sync_ids()
 
             def run_n(n):
@@ -347,6 +369,8 @@ def host_runner_bench_tp(args, torch, decoder, ops, cfg, spec, sess, comm, batch
 
             med, times = timed_blocks(run_n, steps, blocks, world, dev, sync=stream.synchronize, before_block=lambda: m.requests_rewind(SEQ_LEN))
             last = m.sync_ids()
+            if outputs is not None:
+                outputs.update(logits=model_tensor(m, "logits"), next_ids=last)
     finally:
         m.close()
     return {"fused_graph": {"tokens_per_s": round(batch * steps / med, 2), "ms_per_step": round(med / steps * 1e3, 4), "blocks": blocks_summary(times, steps),
@@ -355,9 +379,10 @@ def host_runner_bench_tp(args, torch, decoder, ops, cfg, spec, sess, comm, batch
                             "lm_head": "K-split Gemm + AllReduce (the reference's TP tail)", "last_ids": last[:4]}}
 
 
-def prefill_bench(args, torch, decoder, ops):
+def prefill_bench(args, torch, decoder, ops, outputs):
     """--workload prefill_2048 (see WORKLOADS).  Timed with HIP events on the launch stream around whole prefill calls (eager
-    launches: the context phase is not graph-captured); the attention kernel alone is timed the same way over all layers' calls."""
+    launches: the context phase is not graph-captured); with --full, the attention kernel alone is timed the same way over all
+    layers' calls, and every GEMM of a layer alone."""
     wbits, group, kv_mode, batch, gptq = WORKLOADS["prefill_2048"]
     cfg = decoder.QWEN2_7B
     L = 2048
@@ -369,29 +394,72 @@ def prefill_bench(args, torch, decoder, ops):
     prompt = [int(t) for t in torch.randint(0, cfg.vocab, (L,), generator=gen)]
     t_build = time.time() - t0
     nl = len(model.layers)
-    for _ in range(max(1, args.warmup)):
-        sess.prefill([prompt])
-    torch.cuda.synchronize()
     steps = max(1, args.steps)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t_wall = time.perf_counter()
-    e0.record()
-    for _ in range(steps):
-        sess.prefill([prompt])
-    e1.record()
-    torch.cuda.synchronize()
-    t_wall = (time.perf_counter() - t_wall) / steps
-    ms = e0.elapsed_time(e1) / steps
+    python_outputs = {}
+
+    def time_python_runner():
+        for _ in range(max(1, args.warmup)):
+            sess.prefill([prompt])
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t_wall = time.perf_counter()
+        e0.record()
+        for _ in range(steps):
+            lo = sess.prefill([prompt])
+        e1.record()
+        torch.cuda.synchronize()
+        t_wall = (time.perf_counter() - t_wall) / steps
+        if args.dump_outputs:
+            python_outputs.update(logits=lo.float().cpu().numpy(), next_ids=sess.ids.cpu().numpy())
+        return e0.elapsed_time(e1) / steps, t_wall
+
+    # a plain run times the path `value` comes from: the C++ operator layer, or the Python session where that does not run
+    ms = t_wall = None
+    if args.full or not host_leg:
+        ms, t_wall = time_python_runner()
     # the same context phase through the C++ operator layer: serialized reference graph -> fusion pass -> OpFactory(HIP) -> model runner
     # (request_start = AsModel's context phase of one request: PreProcessId, embedding, the fused layers at M = 2048, GetLastLine, lm_head,
     # GenerateOp), over the Python session's span pool
     host = None
+    host_outputs = {}
     if host_leg:
         try:
-            host = prefill_host_bench(args, torch, ops, model, sess, prompt, steps)
+            host = prefill_host_bench(args, torch, ops, model, sess, prompt, steps, outputs=host_outputs if args.dump_outputs else None)
         except Exception as e:  # the line must still be printed: the Python session's figure stands
             host = {"error": f"{type(e).__name__}: {e}"[:300]}
+    value_from_host = bool(host and "ms_per_prompt" in host and host.get("fused"))
+    if not value_from_host and ms is None:
+        ms, t_wall = time_python_runner()
+    outputs.update(host_outputs if value_from_host else python_outputs)
+    out_d = {
+        "metric": "prefill (context phase) tokens/sec, Qwen2-7B weight-only quantized, one 2048-token prompt",
+        "value": None, "unit": "tokens/s", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
+        "ms_per_step": None, "higher_is_better": True, "runner": "python: decoder.DecodeSession.prefill (ctypes over the C-ABI)",
+        "python_runner": {"tokens_per_s": round(L / (ms * 1e-3), 1), "ms_per_prompt": round(ms, 3)} if ms is not None else None,
+        "host_runner": host, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
+        "data": "synthetic (random-init InstantQuant weights of the Qwen2-7B shapes, random prompt)",
+        "config": {"workload": f"Qwen2-7B prefill_2048: int{wbits} weight-only group {group}, 16-bit KV spans, batch 1, prompt {L} tokens, "
+                               f"{nl} layers, eager launches (DecodeSession.prefill)", "global_batch": 1, "seq_len": L, "parallelism": "tp1",
+                   "layers": nl},
+        "build_s": round(t_build, 1),
+    }
+    if ms is not None:
+        out_d["value"], out_d["ms_per_step"] = round(L / (ms * 1e-3), 1), round(ms, 3)
+    if args.full:
+        out_d.update(prefill_kernels(torch, ops, model, sess, cfg, wbits, group, L, ms, t_wall))
+    if value_from_host:  # as for the decode workloads: `value` is the C++ operator layer's figure
+        out_d["value"], out_d["ms_per_step"] = host["tokens_per_s"], host["ms_per_prompt"]
+        out_d["runner"] = "host: C++ operator layer -- serialized reference graph -> fusion pass -> OpFactory(HIP) -> model runner (context phase, eager)"
+    if args.layers is not None:
+        out_d["invalid"] = "debug run with a truncated layer stack"
+    return out_d
+
+
+def prefill_kernels(torch, ops, model, sess, cfg, wbits, group, L, ms, t_wall):
+    """--full, prefill_2048: the attention kernel and every GEMM of a layer alone, each timed with HIP events -> roofline, attention,
+    gemms and context_phase of the record (`ms`, `t_wall`: the Python session's whole prefill)."""
+    nl = len(model.layers)
     # the attention kernel alone: all layers' calls on resident fused qkv rows
     n, g, H = cfg.n_heads, cfg.n_kv, cfg.head_dim
     qkv = (torch.randn(L, (n + 2 * g) * H, device="cuda") * 0.5).to(torch.bfloat16)
@@ -439,15 +507,7 @@ def prefill_bench(args, torch, decoder, ops):
     gemm_flops = 2.0 * L * sum(p.N * p.K for lw_ in model.layers for p in (lw_.qkv, lw_.o, lw_.gate, lw_.up, lw_.down))
     dom = gemms["gate_up_swiglu_gemm"]
     dom_flops = 2.0 * L * 2 * lw.gate.N * lw.gate.K
-    out_d = {
-        "metric": "prefill (context phase) tokens/sec, Qwen2-7B weight-only quantized, one 2048-token prompt",
-        "value": round(L / (ms * 1e-3), 1), "unit": "tokens/s", "n_gpus": 1, "steps": steps, "warmup": args.warmup,
-        "ms_per_step": round(ms, 3), "higher_is_better": True, "runner": "python: decoder.DecodeSession.prefill (ctypes over the C-ABI)",
-        "python_runner": {"tokens_per_s": round(L / (ms * 1e-3), 1), "ms_per_prompt": round(ms, 3)}, "host_runner": host, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
-        "data": "synthetic (random-init InstantQuant weights of the Qwen2-7B shapes, random prompt)",
-        "config": {"workload": f"Qwen2-7B prefill_2048: int{wbits} weight-only group {group}, 16-bit KV spans, batch 1, prompt {L} tokens, "
-                               f"{nl} layers, eager launches (DecodeSession.prefill)", "global_batch": 1, "seq_len": L, "parallelism": "tp1",
-                   "layers": nl},
+    return {
         # the kernel the context phase spends most of its time in (the launch includes the RMSNorm kernel in front of it)
         "roofline": {"bound": "mfma", "kernel": "dihip::gemm_prefill_kernel<4, bf16, SwiGLU> (RMSNorm + gate/up weight-only GEMM + SwiGLU, M = 2048)",
                      "achieved": dom["tflops"], "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(dom["tflops"] / MFMA_BF16_PEAK_TFLOPS, 4),
@@ -458,17 +518,10 @@ def prefill_bench(args, torch, decoder, ops):
         "gemms": gemms,
         "context_phase": {"attention_share": round(attn_us * nl / (ms * 1e3), 4), "gemm_tflops_if_rest_were_gemm": round(
             gemm_flops / max(1e-9, (ms * 1e-3 - attn_us * nl * 1e-6)) / 1e12, 1), "host_wall_ms": round(t_wall * 1e3, 3)},
-        "build_s": round(t_build, 1),
     }
-    if host and "ms_per_prompt" in host and host.get("fused"):  # as for the decode workloads: `value` is the C++ operator layer's figure
-        out_d["value"], out_d["ms_per_step"] = host["tokens_per_s"], host["ms_per_prompt"]
-        out_d["runner"] = "host: C++ operator layer -- serialized reference graph -> fusion pass -> OpFactory(HIP) -> model runner (context phase, eager)"
-    if args.layers is not None:
-        out_d["invalid"] = "debug run with a truncated layer stack"
-    return out_d
 
 
-def prefill_host_bench(args, torch, ops, model, sess, prompt, steps):
+def prefill_host_bench(args, torch, ops, model, sess, prompt, steps, outputs=None):
     from dash_infer_amd import hostapi
     from dash_infer_amd import ref_graph
     cfg = model.cfg
@@ -502,13 +555,15 @@ def prefill_host_bench(args, torch, ops, model, sess, prompt, steps):
             stream.synchronize()
             t_wall = (time.perf_counter() - t_wall) / steps
             ms = e0.elapsed_time(e1) / steps
+            if outputs is not None:   # --dump-outputs: the last prompt's logits (the lm_head row) and first generated id
+                outputs.update(logits=model_tensor(m, "logits"), next_ids=[first])
         finally:
             m.close()
     return {"tokens_per_s": round(L / (ms * 1e-3), 1), "ms_per_prompt": round(ms, 3), "host_wall_ms": round(t_wall * 1e3, 3), "fused": rep["fused"],
             "operators": rep["ops"], "first_token": int(first) if first is not None else None}
 
 
-def moe_layer_bench(args, torch, ops):
+def moe_layer_bench(args, torch, ops, outputs):
     """--workload moe_layer: one "step" = the mixture-of-experts block of all 28 layers for a batch of 16 tokens (each layer
     its own 64-expert stack: 49 GB, nothing cache-resident).  Algorithmic bytes per layer: every (token, expert) slot streams
     3 * hidden * width int8 weights + scales unless another slot of the step picked the same expert; counted per distinct
@@ -553,6 +608,8 @@ def moe_layer_bench(args, torch, ops):
         gr.replay()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        outputs["out"] = out.float().cpu().numpy()
     ms = elapsed / args.steps * 1e3
     bytes_step = distinct * (3 * hidden * proj + 2 * (2 * proj + hidden) * 2)  # int8 weights + bf16 (scale, zero) per column
     gbs = bytes_step / (ms * 1e-3) / 1e9
@@ -764,7 +821,7 @@ def secondary_workloads(names=("int4_b32_u4kv", "int8_b1", "prefill_2048", "cfg3
             res.append({"workload": w, "skipped": "wall budget of this run spent (DIHIP_BENCH_BUDGET_S)"})
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", str(steps if w != "prefill_2048" else 3),
-               "--warmup", str(warmup if w != "prefill_2048" else 1), "--blocks", "3", "--no-cpu-baseline", "--no-extra"]
+               "--warmup", str(warmup if w != "prefill_2048" else 1), "--blocks", "3", "--no-cpu-baseline", "--no-extra", "--full"]
         t0 = time.time()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout if left is None else max(20, min(timeout, left)), cwd=ROOT)
@@ -810,7 +867,7 @@ def rocprof_kernel_stats(workload, steps=16, warmup=4, timeout=300):
     d = tempfile.mkdtemp(prefix="dihip_prof_", dir="/tmp")
     cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "b", "--", sys.executable, os.path.abspath(__file__),
            "--workload", workload, "--steps", str(steps), "--warmup", str(warmup), "--blocks", "2", "--no-cpu-baseline", "--no-extra",
-           "--runner", "python"]
+           "--runner", "python", "--full"]
     try:
         env = dict(os.environ, TMPDIR="/tmp", DIHIP_BENCH_ROCPROF="0")
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd="/tmp", env=env)
@@ -888,7 +945,7 @@ def pmc_traffic_live(workload, timeout=150):
         for ctr, mult in (("FETCH_SIZE", 2), ("WRITE_SIZE", 1)):
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", os.path.join(d, ctr), "-o", "pmc", "--", sys.executable,
                    os.path.abspath(__file__), "--workload", workload, "--steps", "3", "--warmup", "1", "--blocks", "1", "--layers", "6",
-                   "--no-cpu-baseline", "--no-graph", "--runner", "python", "--no-extra"]
+                   "--no-cpu-baseline", "--no-graph", "--runner", "python", "--no-extra", "--full"]
             env = dict(os.environ, TMPDIR="/tmp", DIHIP_BENCH_ROCPROF="0", DIHIP_BENCH_PMC="0")
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd="/tmp", env=env)
             files = glob.glob(os.path.join(d, ctr, "**", "*counter_collection*.csv"), recursive=True)
@@ -922,6 +979,45 @@ def write_detail(out):
         return os.path.relpath(p, ROOT)
     except OSError:
         return None
+
+
+def model_tensor(m, name):
+    """Host copy of a tensor the C++ operator layer's model owns (hostapi.Model.get_tensor: dtype code, shape, device pointer),
+    as float32 rows [-1, last dim]; the copy is exactly the tensor's own size."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    dt, shp, p = m.get_tensor(name)
+    raw = {1: np.float32, 2: np.float16, 9: np.uint16}[dt]   # f32, f16, bf16 (hostapi.DT)
+    a = np.empty(int(np.prod(shp)), dtype=raw)
+    torch.cuda.synchronize()
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMemcpy.restype = C.c_int
+    if a.nbytes and hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(p), a.nbytes, 2) != 0:   # 2: hipMemcpyDeviceToHost
+        raise RuntimeError(f"hipMemcpy of model tensor {name} failed")
+    if dt == 9:
+        a = (a.astype(np.uint32) << 16).view(np.float32)
+    return a.astype(np.float32).reshape(-1, shp[-1] if shp else 1)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: {name: array} -> d/<name>.npy, float32 (token ids float64, exact).  An array beyond its share of the 64 MB
+    budget is written as a fixed, seeded sample of its elements: d/<name>_sample.npy beside d/<name>_sample_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in sorted(arrays.items()):
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.kind in "iub" else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, (share - 4096) // (a.itemsize + 8), replace=False))   # 4 KB: the .npy headers
+            np.save(os.path.join(d, name + "_sample_index.npy"), idx.astype(np.float64))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _short(sv, n):
@@ -1037,13 +1133,22 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="debug: eager launches instead of hipGraph replay")
     ap.add_argument("--steps-per-graph", type=int, default=1,
                     help="consecutive decode steps captured per hipGraph (measured: 1 is fastest, back-to-back replays already pipeline)")
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps each; the median block is reported")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of --steps steps each; the median block is reported (default: 1 block, 5 with --full)")
     ap.add_argument("--runner", default="auto", choices=["auto", "python", "host"],
                     help="whose step `value` is: the C++ operator layer (host: reference operator list -> fusion pass -> OpFactory -> "
                          "model runner, hipGraph replay) or decoder.DecodeSession (python: the same C-ABI calls from Python).  auto = host "
-                         "where it applies (one GPU, dense model), python otherwise; both figures are always in the line")
-    ap.add_argument("--no-extra", action="store_true", help="headline only: no host-runner figures, no secondary workloads, no TP A/B")
+                         "where it applies (one GPU, dense model), python otherwise; --full puts both figures in the line")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no unfused host-runner figures, no secondary workloads, no TP A/B")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: both runners' figures, the unfused list, per-kernel breakdown and roofline (rocprofv3, "
+                         "PMC), CPU baselines, secondary workloads, TP all-reduce share and A/B, the detail file.  Without it a run sets up, "
+                         "warms up, times --steps steps of the path `value` comes from and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (logits, next token ids, ...) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
 
     t_main = time.time()
     import torch
@@ -1086,13 +1191,19 @@ def main():
                                  allow_labelled_fallback=True)
 
     wbits, group, kv_mode, batch, gptq = WORKLOADS[args.workload]
+    outputs = {}   # --dump-outputs: what the timed path computed in its last step
     if args.workload == "prefill_2048":
         assert world == 1, "prefill_2048 is a one-GPU workload"
-        print(json.dumps(prefill_bench(args, torch, decoder, ops)), flush=True)
+        out = prefill_bench(args, torch, decoder, ops, outputs)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
+        print(json.dumps(out), flush=True)
         return
     if args.workload == "moe_layer":
         assert world == 1, "moe_layer is a one-GPU workload"
-        out = moe_layer_bench(args, torch, ops)
+        out = moe_layer_bench(args, torch, ops, outputs)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
         return
     global SEQ_LEN
@@ -1159,34 +1270,52 @@ def main():
             sess.step()
 
     graph_on = not args.no_graph
-    if graph_on:
-        try:
-            sess.capture(warmup=1, steps_per_graph=max(1, args.steps_per_graph))
-            run_n = sess.replay_steps
-        except Exception as e:  # noqa: BLE001 -- e.g. a collective that refuses stream capture: measure eager launches
-            print(f"[rank {rank}] hipGraph capture failed ({type(e).__name__}: {e}); timing eager launches", file=sys.stderr)
-            graph_on = False
-            torch.cuda.synchronize()
-            sess.set_state(ids, [SEQ_LEN] * batch)
-            run_n = run_eager
-    else:
+    python_outputs = {}
+
+    def time_python_runner():
+        """decoder.DecodeSession's step: capture (unless --no-graph), warm-up, timed blocks -> (median block s, block times)"""
+        nonlocal graph_on
         run_n = run_eager
-    run_n(args.warmup)
-    # exactly K decode steps per block (graphs of --steps-per-graph consecutive steps + single-step graphs), barrier + synchronize
-    # on both sides, max over ranks; the median of --blocks blocks is the reported time
-    elapsed, block_times = timed_blocks(run_n, args.steps, blocks, world, torch.device("cuda", local_rank),
-                                        before_block=lambda: sess.set_state(ids, [SEQ_LEN + args.warmup] * batch))
-    last_ids = sess.ids.tolist()
-    python_runner = {"tokens_per_s": round(batch * args.steps / elapsed, 2), "ms_per_step": round(elapsed / args.steps * 1e3, 4)}
+        if graph_on:
+            try:
+                sess.capture(warmup=1, steps_per_graph=max(1, args.steps_per_graph))
+                run_n = sess.replay_steps
+            except Exception as e:  # noqa: BLE001 -- e.g. a collective that refuses stream capture: measure eager launches
+                print(f"[rank {rank}] hipGraph capture failed ({type(e).__name__}: {e}); timing eager launches", file=sys.stderr)
+                graph_on = False
+                torch.cuda.synchronize()
+                sess.set_state(ids, [SEQ_LEN] * batch)
+        run_n(args.warmup)
+        if settle_steps(args):
+            sess.set_state(ids, [SEQ_LEN + args.warmup] * batch)
+            run_n(settle_steps(args))
+        # exactly K decode steps per block (graphs of --steps-per-graph consecutive steps + single-step graphs), barrier + synchronize
+        # on both sides, max over ranks; the median of --blocks blocks is the reported time
+        med, times = timed_blocks(run_n, args.steps, blocks, world, torch.device("cuda", local_rank),
+                                  before_block=lambda: sess.set_state(ids, [SEQ_LEN + args.warmup] * batch))
+        if args.dump_outputs:
+            python_outputs.update(logits=sess.logits.float().cpu().numpy(), next_ids=sess.ids.cpu().numpy())
+        return med, times
+
+    # A plain run times the path `value` comes from and nothing else: the C++ operator layer where it runs (one GPU; every rank's
+    # runner at TP > 1), the Python runner where it does not or fails.  --full times the Python runner first, as the record always had it.
+    host_tp_leg = world > 1 and args.runner != "python" and os.environ.get("DIHIP_BENCH_HOST_TP", "1") != "0" and cfg.moe is None
+    elapsed = block_times = last_ids = python_runner = None
+    if args.full or not (host_leg or host_tp_leg):
+        elapsed, block_times = time_python_runner()
+        last_ids = sess.ids.tolist()
+        python_runner = {"tokens_per_s": round(batch * args.steps / elapsed, 2), "ms_per_step": round(elapsed / args.steps * 1e3, 4)}
     host_runner = None
+    host_outputs = {}
     if host_leg:
         try:
             host_runner = {"fused_graph": host_runner_bench(args, torch, decoder, ops, model, sess, batch, max_len, kv_mode, True, True,
-                                                            args.steps, blocks)}
-            if not args.no_extra:   # the reference's own operator list, one launch per operator, eager: what fusion + capture buy
+                                                            args.steps, blocks, outputs=host_outputs if args.dump_outputs else None)}
+            if args.full and not args.no_extra:   # the reference's own operator list, one launch per operator, eager: what fusion + capture buy
                 host_runner["unfused_eager"] = host_runner_bench(args, torch, decoder, ops, model, sess, batch, max_len, kv_mode, False,
                                                                  False, max(4, args.steps // 4), min(blocks, 3))
-            host_runner["fused_graph_vs_python_runner"] = round(host_runner["fused_graph"]["tokens_per_s"] / python_runner["tokens_per_s"], 4)
+            if python_runner:
+                host_runner["fused_graph_vs_python_runner"] = round(host_runner["fused_graph"]["tokens_per_s"] / python_runner["tokens_per_s"], 4)
         except Exception as e:  # noqa: BLE001 -- never lose the headline number to the second runner
             if args.runner == "host":
                 raise
@@ -1203,23 +1332,31 @@ def main():
         dist.destroy_process_group()
         if isinstance(host_runner, dict):
             host_runner["tp_leg_selftest_one_rank"] = selftest
-    if world > 1 and args.runner != "python" and os.environ.get("DIHIP_BENCH_HOST_TP", "1") != "0" and cfg.moe is None:
+    if host_tp_leg:
         host_runner = host_runner_bench_tp(args, torch, decoder, ops, cfg, spec, sess, comm, batch, max_len, kv_mode, rank, world, local_rank,
-                                           args.steps, blocks)
-        if "fused_graph" in host_runner:
+                                           args.steps, blocks, outputs=host_outputs if args.dump_outputs else None)
+        if "fused_graph" in host_runner and python_runner:
             host_runner["fused_graph_vs_python_runner"] = round(host_runner["fused_graph"]["tokens_per_s"] / python_runner["tokens_per_s"], 4)
     value_from_host = isinstance(host_runner, dict) and "fused_graph" in host_runner and host_runner["fused_graph"].get("fused")
     if value_from_host:
         elapsed = host_runner["fused_graph"]["ms_per_step"] * 1e-3 * args.steps
         block_times = None
+        outputs = host_outputs
+        last_ids = last_ids or host_runner["fused_graph"].get("last_ids")
+    else:
+        if python_runner is None:   # plain run, the operator layer gave no figure: the Python runner's is `value`, as in a full run
+            elapsed, block_times = time_python_runner()
+            last_ids = sess.ids.tolist()
+            python_runner = {"tokens_per_s": round(batch * args.steps / elapsed, 2), "ms_per_step": round(elapsed / args.steps * 1e3, 4)}
+        outputs = python_outputs
 
     # share of the step spent in the tensor-parallel all-reduces: the step's collectives alone (2 per layer on the hidden rows,
     # same backend, same message), captured into a graph and replayed between events -- every rank takes part
-    ar_info = allreduce_alone(torch, comm, sess, len(model.layers), graph_on, elapsed / args.steps * 1e3, world) if world > 1 else None
+    ar_info = allreduce_alone(torch, comm, sess, len(model.layers), graph_on, elapsed / args.steps * 1e3, world) if world > 1 and args.full else None
     # one SCALE invocation answers DESIGN section 4's open questions: RCCL vs the one-shot peer-to-peer all-reduce, each with the
     # all-reduce on the compute stream and overlapped on a side stream beside a weight prefetch -- the SAME model, same process
     tp_ab = None
-    if world > 1 and not args.no_extra:
+    if world > 1 and args.full and not args.no_extra:
         tp_ab = tp_ab_runs(args, torch, decoder, model, comm, batch, max_len, kv_mode, ids, rank, world, local_rank)
 
     ms_per_step = elapsed / args.steps * 1e3
@@ -1261,7 +1398,7 @@ def main():
         "lm_head_split": getattr(model, "lm_split", "vocab") if world > 1 else None,
         "build_s": round(t_build, 1),
         "workload_key": args.workload,
-        "last_ids": last_ids[:4],
+        "last_ids": (last_ids or [])[:4],
         **({"distinct_routed_experts_per_layer": distinct_experts} if distinct_experts is not None else {}),
     }
     if args.layers is not None:
@@ -1277,10 +1414,10 @@ def main():
     if rank == 0:
         budget = float(os.environ.get("DIHIP_BENCH_BUDGET_S", "420"))   # wall budget of the whole run; the headline prints regardless
         deadline = t_main + budget
-        full = args.workload == "int4_b1" and world == 1 and not args.no_extra and args.layers is None
+        full = args.full and args.workload == "int4_b1" and world == 1 and not args.no_extra and args.layers is None
         try:
-            if cfg.moe is not None:
-                raise StopIteration  # the per-kernel breakdown below is the dense layer's
+            if cfg.moe is not None or not args.full:
+                raise StopIteration  # the per-kernel breakdown below is the dense layer's, and a run of its own (--full)
             kb = kernel_breakdown(sess, torch, ops)
             gpt = 1 if (group > 0 and group == (128 if wbits == 4 else 64)) else 0
             if batch <= 4:
@@ -1350,7 +1487,7 @@ def main():
             pass
         except Exception as e:  # never lose the headline number to the breakdown
             out["roofline_error"] = repr(e)[:300]
-        if world == 1 and not args.no_cpu_baseline and args.workload in ("int4_b1", "int8_b1", "int4_b32_u4kv"):  # the CPU graph below is Qwen2-7B's
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload in ("int4_b1", "int8_b1", "int4_b32_u4kv"):  # the CPU graph below is Qwen2-7B's
             try:
                 out["cpu_baseline"] = cpu_baseline_torch(wbits, group, budget_s=12.0)
             except Exception as e:
@@ -1370,7 +1507,9 @@ def main():
         if full:
             out["extra"] = {"workloads": secondary_workloads(deadline=deadline)}
         out["wall_s"] = round(time.time() - t_main, 1)
-        detail = write_detail(out)
+        detail = write_detail(out) if args.full else None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(headline_line(out, detail)), flush=True)   # ONE line, small, LAST: what the driver parses
     if world > 1:
         import torch.distributed as dist

@@ -5,11 +5,12 @@
 TAG=${1:-pmc}
 WL=${2:-int4_b1}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $OUT/${WL}_$ctr -o pmc -- python $GRAFT_REPO_ROOT/bench.py --workload $WL --steps 4 --warmup 2 --blocks 1 --no-cpu-baseline --no-graph --runner python --no-extra > $OUT/${WL}_$ctr.json 2> $OUT/${WL}_$ctr.err
+  timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $OUT/${WL}_$ctr -o pmc -- python $ROOT/bench.py --workload $WL --steps 4 --warmup 2 --blocks 1 --no-cpu-baseline --no-graph --runner python --no-extra --full > $OUT/${WL}_$ctr.json 2> $OUT/${WL}_$ctr.err
   echo "$WL $ctr exit $?"
   ls $OUT/${WL}_$ctr | head -3
 done

@@ -12,7 +12,7 @@ if [ -z "$SKIP_TESTS" ]; then
   DIHIP_FULL_DEPTH_ABLATION=${ABLATION:-0} timeout 2400 python -m pytest tests -m gpu -q -s --timeout 900 2>&1 | grep -E "FULL DEPTH|configs\[|7B-width|operator graph|\[int4_b1\]|\[int4_b32_u4kv\]|\[cfg3_rank\]|\[kv codec|\[deferred norm|\[prefill tail|passed|failed|error" | cut -c1-900 > $OUT/pytest_gpu.log
   tail -3 $OUT/pytest_gpu.log
 fi
-( time timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err ) 2> $OUT/bench_default_time.txt
+( time timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err ) 2> $OUT/bench_default_time.txt
 cp gpurun_out/bench_detail.json $OUT/bench_detail.json 2>/dev/null
 python - <<PY
 import json
@@ -41,7 +41,7 @@ done
 export TMPDIR=/tmp
 cd /tmp
 for w in int4_b1 int8_b1 int4_b32_u4kv cfg3_rank tp8_rank_7b prefill_2048; do
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$w -o $w -- python $ROOT/bench.py --workload $w --no-cpu-baseline --no-extra > $OUT/prof_bench_$w.json 2> $OUT/prof_bench_$w.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$w -o $w -- python $ROOT/bench.py --workload $w --no-cpu-baseline --no-extra --full > $OUT/prof_bench_$w.json 2> $OUT/prof_bench_$w.err
   f=$(find $OUT/prof_$w -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp "$f" $OUT/bench_${w}_kernel_stats.csv && echo "== $w" && grep dihip $OUT/bench_${w}_kernel_stats.csv | head -8 | cut -d, -f1-4 | cut -c1-170
   find $OUT/prof_$w -name "*.csv" -size +4M -delete
