@@ -44,6 +44,16 @@ _SIGS = {
     "dihip_rowsq_bytes": (sz, []),
     "dihip_gemm_prefill_tail_parts": (i32, [i32, i32, i32, i32, i32, i32]),
     "dihip_gemm_lowp_prefers_frag": (i32, [i32, i32, i32, i32, i32, i32]),
+    "dihip_gemm_a8w8_workspace_bytes": (sz, [i32, i32, i32]),
+    "dihip_act_quant_i8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "dihip_norm_act_quant_i8": (i32, [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, sz]),
+    "dihip_gemm_a8w8_q": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32]),
+    "dihip_gemm_a8w8_swiglu_q": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
+    "dihip_gemm_a8w8_addto_q": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
+    "dihip_gemm_a8w8": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, i32]),
+    "dihip_a8w8_norm_gemm": (i32, [vp, vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, i32]),
+    "dihip_a8w8_norm_swiglu": (i32, [vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, i32]),
+    "dihip_a8w8_gemm_addto": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, i32]),
     "dihip_moe_route": (i32, [vp, vp, i32, i32, i32, vp, vp, i32]),
     "dihip_rmsnorm_rows": (i32, [vp, vp, vp, vp, f32, i32, i32, i32]),
     "dihip_moe_route_ep": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32]),

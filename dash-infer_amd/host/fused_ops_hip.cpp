@@ -20,6 +20,8 @@
 //   DihipMoeBlock       <- the mixture-of-experts feed-forward block of qwen_v20_moe.py:318-382 (twelve operators)
 //   DihipLMHead         <- LayerNormNoBeta + GetLastLine + Gemm(lm_head)  f32 logits
 //   DihipGreedy         <- GenerateOp (greedy requests); advances the device-resident length counters in the same launch
+// The projections may also be GemmA8W8 (attribute act_quant = 1 on DihipNormGemm / DihipGemmAddTo / DihipNormSwiGLU): the context
+// phase then runs the int8 x int8 entry points (dihip_a8w8_*), the decoder phase is unchanged.
 //
 // Activation layouts between two fused operators (row-major / DIHIP_ACT_FRAG32) are negotiated through HIPContext: the consumer
 // advertises its GEMM shape for the tensor at Init, the producer decides at Reshape when the row count is known
@@ -128,6 +130,19 @@ int read_group(const OperatorProto& p) {
   const char* a = attr_ptr(p, "GroupSize");
   return a ? *(const int*)a : -1;
 }
+// act_quant = 1 (fusion_pass.cpp: built from GemmA8W8 operators): in the CONTEXT phase the operator quantises its activation rows
+// to int8 and runs the int8 x int8 GEMM (dihip_a8w8_*, include/dashinfer_hip.h section 1c) on the same packed weight; the decoder
+// phase is what it is without the attribute (GemmA8W8GPU does the same: gemm_a8w8_gpu.cpp:216, 268).  int8 per-channel weights only.
+bool read_act_quant(const OperatorProto& p) {
+  const char* a = attr_ptr(p, "act_quant");
+  return a && *(const int*)a != 0;
+}
+bool act_quant_ok(const OperatorProto& p) { return !read_act_quant(p) || (read_wbits(p) == 8 && read_group(p) == -1); }
+// the workspace of both phases: Forward only enqueues
+size_t lowp_workspace_bytes(bool act_quant, int wbits, int m, int n, int k, int group) {
+  const size_t a16 = dihip_gemm_lowp_workspace_bytes(wbits, std::max(m, 1), n, k, group);
+  return act_quant ? std::max(a16, dihip_gemm_a8w8_workspace_bytes(std::max(m, 1), n, k)) : a16;
+}
 
 // ---- the attention half of a batch-1 decode layer as ONE launch (dihip_decode_attn_block, round 5) ---------------------------------
 // DihipNormGemm(qkv) -> DihipRopeSpanAttn -> DihipGemmAddTo(o) stay three operators of the list (context phase, batches, quantised
@@ -218,6 +233,8 @@ class DihipNormGemmOp : public AsOperator, public AttnBlockQkvPart {
     if (!e) return AsStatus::ALLSPARK_PARAM_ERROR;  // layernorm_nobeta_op.cpp:69-73
     eps_ = *(const float*)e;
     if (const char* a = attr_ptr(op_proto, "activation")) act_ = *(const int*)a;
+    if (!act_quant_ok(op_proto)) return AsStatus::ALLSPARK_PARAM_ERROR;
+    act_quant_ = read_act_quant(op_proto);
     AS_CHECK_STATUS(w_.Pack(op_name_, read_wbits(op_proto), read_group(op_proto), weights_[1], weights_[2], weights_[3], stream_of(&ctx)));
     if ((int)weights_[0]->GetShape()[0] != w_.k || weights_[0]->GetDataType() != w_.ft) return AsStatus::ALLSPARK_PARAM_ERROR;
     sync_ = zeroed(op_name_ + ".sync", dihip_gemm_lowp_sync_bytes(), stream_of(&ctx));
@@ -250,7 +267,7 @@ class DihipNormGemmOp : public AsOperator, public AttnBlockQkvPart {
     AsTensor* y = tensor_map_->at(out_names_[0]).get();
     y->SetDataType(w_.ft);
     AS_CHECK_STATUS(y->SetShape(std::move(s)));
-    return grow_workspace(tensor_map_, dihip_gemm_lowp_workspace_bytes(w_.wbits, std::max(m_, 1), w_.n, w_.k, w_.group));
+    return grow_workspace(tensor_map_, lowp_workspace_bytes(act_quant_, w_.wbits, m_, w_.n, w_.k, w_.group));
   }
   AsStatus Forward(RuntimeContext* rt) override {
     if (skip_) return AsStatus::ALLSPARK_SUCCESS;  // part of the o-projection's single launch (AttnBlockQkvPart)
@@ -259,6 +276,9 @@ class DihipNormGemmOp : public AsOperator, public AttnBlockQkvPart {
     AsTensor* wsp = tensor_map_->at("workspace").get();
     const void* bias = weights_.size() == 5 ? weights_[4]->GetDataPtr() : nullptr;
     hipStream_t s = stream_of(ctx_);
+    if (act_quant_ && rt && rt->is_context)
+      return FromDihip(dihip_a8w8_norm_gemm(s, (const float*)h->GetDataPtr(), weights_[0]->GetDataPtr(), eps_, w_.w->GetDataPtr(), w_.sz->GetDataPtr(),
+                                            bias, y->GetDataPtr(), m_, w_.n, w_.k, act_, wsp->GetDataPtr(), wsp->GetSizeInByte(), DihipDtype(w_.ft)));
     if (in_names_.size() > 1 && norm_fuse_active(ctx_, rt, m_)) {
       AsTensor* xn = tensor_map_->at(in_names_[1]).get();
       const RowNormState rn = hip_ctx(ctx_).RowNorm(in_names_[1]);  // (parts == 0: the finished norm)
@@ -275,7 +295,7 @@ class DihipNormGemmOp : public AsOperator, public AttnBlockQkvPart {
   PackedLowp w_;
   float eps_ = 1e-6f;
   int act_ = 0, m_ = 0;
-  bool skip_ = false;
+  bool skip_ = false, act_quant_ = false;
   std::unique_ptr<AsTensor> sync_;
 };
 REGISTER_OP(DihipNormGemm, HIP, DihipNormGemmOp)
@@ -293,6 +313,8 @@ class DihipNormSwiGLUOp : public AsOperator {
     if (!e) return AsStatus::ALLSPARK_PARAM_ERROR;
     eps_ = *(const float*)e;
     const int wb = read_wbits(op_proto), grp = read_group(op_proto);
+    if (!act_quant_ok(op_proto)) return AsStatus::ALLSPARK_PARAM_ERROR;
+    act_quant_ = read_act_quant(op_proto);
     AS_CHECK_STATUS(g_.Pack(op_name_ + ".gate", wb, grp, weights_[1], weights_[2], weights_[3], stream_of(&ctx)));
     AS_CHECK_STATUS(u_.Pack(op_name_ + ".up", wb, grp, weights_[4], weights_[5], weights_[6], stream_of(&ctx)));
     if (g_.n != u_.n || g_.k != u_.k || g_.ft != u_.ft) return AsStatus::ALLSPARK_PARAM_ERROR;
@@ -318,13 +340,17 @@ class DihipNormSwiGLUOp : public AsOperator {
     hip_ctx(ctx_).SetActLayout(out_names_[0], y_layout_);
     const size_t bytes = frag ? dihip_act_frag_bytes(m_, g_.n) : (size_t)m_ * g_.n * SizeofType(g_.ft);
     AS_CHECK_STATUS(ensure_capacity_zeroed(y, bytes, std::move(s), stream_of(ctx_)));
-    return grow_workspace(tensor_map_, dihip_gemm_lowp_workspace_bytes(g_.wbits, std::max(m_, 1), g_.n, g_.k, g_.group));
+    return grow_workspace(tensor_map_, lowp_workspace_bytes(act_quant_, g_.wbits, m_, g_.n, g_.k, g_.group));
   }
   AsStatus Forward(RuntimeContext* rt) override {
     AsTensor* h = tensor_map_->at(in_names_[0]).get();
     AsTensor* y = tensor_map_->at(out_names_[0]).get();
     AsTensor* wsp = tensor_map_->at("workspace").get();
     hipStream_t s = stream_of(ctx_);
+    if (act_quant_ && rt && rt->is_context)  // (the context phase writes row-major rows: Reshape)
+      return FromDihip(dihip_a8w8_norm_swiglu(s, (const float*)h->GetDataPtr(), weights_[0]->GetDataPtr(), eps_, g_.w->GetDataPtr(), g_.sz->GetDataPtr(),
+                                              u_.w->GetDataPtr(), u_.sz->GetDataPtr(), y->GetDataPtr(), m_, g_.n, g_.k, wsp->GetDataPtr(),
+                                              wsp->GetSizeInByte(), DihipDtype(g_.ft)));
     if (in_names_.size() > 1 && norm_fuse_active(ctx_, rt, m_)) {
       AsTensor* xn = tensor_map_->at(in_names_[1]).get();
       const RowNormState rn = hip_ctx(ctx_).RowNorm(in_names_[1]);
@@ -343,6 +369,7 @@ class DihipNormSwiGLUOp : public AsOperator {
   PackedLowp g_, u_;
   float eps_ = 1e-6f;
   int m_ = 0, y_layout_ = DIHIP_ACT_ROWMAJOR;
+  bool act_quant_ = false;
   std::unique_ptr<AsTensor> sync_;
 };
 REGISTER_OP(DihipNormSwiGLU, HIP, DihipNormSwiGLUOp)
@@ -361,6 +388,8 @@ class DihipGemmAddToOp : public AsOperator {
     if (ctx.GetDeviceType() != DeviceType::HIP) return AsStatus::ALLSPARK_PARAM_ERROR;
     if (weights_.size() != 3 && weights_.size() != 4) return AsStatus::ALLSPARK_PARAM_ERROR;
     if (in_names_.size() != 2 || out_names_.empty()) return AsStatus::ALLSPARK_PARAM_ERROR;
+    if (!act_quant_ok(op_proto)) return AsStatus::ALLSPARK_PARAM_ERROR;
+    act_quant_ = read_act_quant(op_proto);
     AS_CHECK_STATUS(w_.Pack(op_name_, read_wbits(op_proto), read_group(op_proto), weights_[0], weights_[1], weights_[2], stream_of(&ctx)));
     has_norm_ = weights_.size() == 4 && out_names_.size() > 1;
     if (has_norm_) {
@@ -444,9 +473,9 @@ class DihipGemmAddToOp : public AsOperator {
       AsTensor* sy = tensor_map_->at("dihip.attn_block_sync").get();
       AS_CHECK_STATUS(FromDihip(dihip_decode_attn_block_prepare(s, sy->GetDataPtr(), sy->GetSizeInByte(), a.n, a.g, a.h, hip_ctx(ctx_).PlanLength())));
     }
-    return grow_workspace(tensor_map_, dihip_gemm_lowp_workspace_bytes(w_.wbits, std::max(m_, 1), w_.n, w_.k, w_.group));
+    return grow_workspace(tensor_map_, lowp_workspace_bytes(act_quant_, w_.wbits, m_, w_.n, w_.k, w_.group));
   }
-  AsStatus Forward(RuntimeContext*) override {
+  AsStatus Forward(RuntimeContext* rt) override {
     AsTensor* x = tensor_map_->at(in_names_[0]).get();
     AsTensor* y = tensor_map_->at(out_names_[0]).get();
     AsTensor* wsp = tensor_map_->at("workspace").get();
@@ -454,6 +483,11 @@ class DihipGemmAddToOp : public AsOperator {
     const float* h_res = add_residual ? (const float*)tensor_map_->at(in_names_[1])->GetDataPtr() : nullptr;
     const int x_layout = hip_ctx(ctx_).ActLayout(in_names_[0]);
     hipStream_t s = stream_of(ctx_);
+    if (act_quant_ && rt && rt->is_context) {  // (context phase: row-major x, no norm hand-on, no attention block -- Reshape)
+      if (x_layout != DIHIP_ACT_ROWMAJOR) return AsStatus::ALLSPARK_INVALID_CALL_ERROR;
+      return FromDihip(dihip_a8w8_gemm_addto(s, x->GetDataPtr(), w_.w->GetDataPtr(), w_.sz->GetDataPtr(), h_res, (float*)y->GetDataPtr(), m_, w_.n,
+                                             w_.k, wsp->GetDataPtr(), wsp->GetSizeInByte(), DihipDtype(w_.ft)));
+    }
     if (block_now_) {
       const AttnBlockQkv q = blk_qkv_->BlockQkv();
       const AttnBlockAttn a = blk_attn_->BlockAttn();
@@ -491,7 +525,7 @@ class DihipGemmAddToOp : public AsOperator {
  private:
   PackedLowp w_;
   float eps_ = 1e-6f;
-  bool has_norm_ = false, norm_now_ = false, block_now_ = false, defer_now_ = false;
+  bool has_norm_ = false, norm_now_ = false, block_now_ = false, defer_now_ = false, act_quant_ = false;
   int m_ = 0, xn_layout_ = DIHIP_ACT_ROWMAJOR;
   std::unique_ptr<AsTensor> rowsq_;
   AttnBlockAttnPart* blk_attn_ = nullptr;

@@ -25,11 +25,14 @@ bool attr_bool(const OperatorProto& p, const char* k) {
 }
 std::string bytes_of(int v) { return std::string(reinterpret_cast<const char*>(&v), sizeof(v)); }
 
-int lowp_bits(const OperatorProto& p) { return p.op_type == "GemmA16W8" ? 8 : p.op_type == "GemmA16W4" ? 4 : 0; }
+// (GemmA8W8: the int8 weight of GemmA16W8 with int8 activations in the context phase, gemm_a8w8_gpu.cpp:45-51)
+bool act_quant(const OperatorProto& p) { return p.op_type == "GemmA8W8"; }
+int lowp_bits(const OperatorProto& p) { return p.op_type == "GemmA16W8" || act_quant(p) ? 8 : p.op_type == "GemmA16W4" ? 4 : 0; }
 
 struct Matcher {
   const std::vector<OperatorProto>& g;
   size_t i = 0;
+  int a8 = -1;  // the list's weight-only Gemms so far: 1 GemmA8W8, 0 GemmA16Wx (a list mixing them stays unfused)
   std::string why;
   bool fail(const std::string& w) {
     if (why.empty()) why = w + (i < g.size() ? " at operator #" + std::to_string(i) + " (" + g[i].op_type + " " + g[i].op_name + ")" : " at the end of the list");
@@ -39,7 +42,10 @@ struct Matcher {
   // a weight-only Gemm that reads `in`, with the expected activation, no residual fused in, plain alpha / layout
   bool lowp(const OperatorProto*& out, const std::string& in, int act, bool bias_ok) {
     const OperatorProto* p = peek();
-    if (!p || !lowp_bits(*p)) return fail("expected GemmA16W8 / GemmA16W4");
+    if (!p || !lowp_bits(*p)) return fail("expected GemmA16W8 / GemmA16W4 / GemmA8W8");
+    if (a8 >= 0 && a8 != (int)act_quant(*p)) return fail("GemmA8W8 mixed with GemmA16W8 / GemmA16W4");
+    if (act_quant(*p) && attr_int(*p, "GroupSize", -1) != -1) return fail("GemmA8W8 is per-channel only");
+    a8 = (int)act_quant(*p);
     if (p->inputs.size() != 1 || p->inputs[0] != in || p->outputs.size() != 1) return fail("weight-only Gemm with unexpected inputs");
     if (p->weights.size() != 3 && !(bias_ok && p->weights.size() == 4)) return fail("weight-only Gemm with unexpected weights (bias)");
     if (attr_int(*p, "activation", 0) != act) return fail("weight-only Gemm with unexpected activation");
@@ -111,6 +117,7 @@ void copy_attr(OperatorProto& dst, const OperatorProto& src, const char* k) {
 void lowp_attrs(OperatorProto& dst, const OperatorProto& gemm) {
   dst.attr["wbits"] = bytes_of(lowp_bits(gemm));
   copy_attr(dst, gemm, "GroupSize");
+  if (act_quant(gemm)) dst.attr["act_quant"] = bytes_of(1);  // context phase: the dihip_a8w8_* entry points
 }
 
 }  // namespace
@@ -192,6 +199,8 @@ std::vector<OperatorProto> FuseDecoderGraph(const std::vector<OperatorProto>& gr
     out.push_back(std::move(f_att));
     xnorm_in.clear();
 
+    if (moe_layer && act_quant(*qkv))
+      return refuse("a mixture-of-experts layer with GemmA8W8 projections is served unfused (" + qkv->op_name + ")");
     if (moe_layer) {
       // the mixture-of-experts feed-forward block (qwen_v20_moe.py:318-382) -> one DihipMoeBlock
       const OperatorProto *router, *moe, *ar_moe, *sgu, *glu, *sdown, *sgate, *calc, *ar_sh, *eadd;

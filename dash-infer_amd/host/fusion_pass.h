@@ -23,6 +23,8 @@ struct FusionReport {
 
 // Pattern table (one decoder layer; tensors are followed by NAME, so operator names are free):
 //   LayerNormNoBeta(h) , GemmA16W8|W4(.; bias)                      -> DihipNormGemm(h [, xnorm of the previous layer])
+//     (GemmA8W8 counts as an 8-bit projection: the fused operators built from it carry act_quant = 1 and run int8 x int8 in the
+//      context phase; a list mixing GemmA8W8 with GemmA16Wx stays unfused)
 //   Rotary(.) , DecOptMQA|DecOptMHA(.)                               -> DihipRopeSpanAttn
 //   GemmA16Wx(.) , [AllReduce] , Binary ADD(., h)                    -> DihipGemmAddTo(+ gamma of the next LayerNormNoBeta) [, AllReduce]
 //   LayerNormNoBeta(h') , GemmA16Wx(.; SILU) , GemmA16Wx(.) , Binary MUL -> DihipNormSwiGLU(h' [, xnorm])

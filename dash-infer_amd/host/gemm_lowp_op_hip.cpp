@@ -1,4 +1,4 @@
-// gemm_lowp_op_hip.cpp -- op types "GemmA16W8" / "GemmA16W4" on DeviceType::HIP.
+// gemm_lowp_op_hip.cpp -- op types "GemmA16W8" / "GemmA16W4" / "GemmA8W8" on DeviceType::HIP.
 // Host logic mirrors GemmA16W8Base::InitV2 / GemmA16W8GPU::{InitV2,Reshape,Forward}
 // (csrc/core/operator/general/gemm_lowp/gemm_a16w8.cpp:21-125, gemm_a16w8_gpu.cpp:30-267) and
 // GemmA16W4GPU (gemm_a16w4_gpu.cpp:26-230): weights [W, scales, zeros, (bias)]; attributes alpha,
@@ -105,7 +105,7 @@ class GemmLowpHIP : public AsOperator {
                         sync_->GetDataPtr(), DihipDtype(ftype_)));
   }
 
- private:
+ protected:
   int m_ = 0, n_ = 0, k_ = 0, group_size_ = -1;
   float alpha_ = 1.0f;
   UnaryType activation_ = UNARYTYPE_UNDEFINED;
@@ -117,5 +117,46 @@ using GemmA16W8HIP = GemmLowpHIP<8>;
 using GemmA16W4HIP = GemmLowpHIP<4>;
 REGISTER_OP(GemmA16W8, HIP, GemmA16W8HIP)
 REGISTER_OP(GemmA16W4, HIP, GemmA16W4HIP)
+
+// "GemmA8W8" (QuantMode.A8W8, quantization_utils.py:65-66): GemmA8W8GPU (gemm_a8w8_gpu.cpp:45-51, 119-271) quantises the
+// activation rows to int8 and multiplies int8 x int8 in the context phase, and runs the A16W8 kernels in the decoder phase.
+// The same here, on ONE packed copy of the weight: context phase dihip_gemm_a8w8 (quantiser + i8 MFMA GEMM), decoder phase
+// exactly GemmA16W8HIP::Forward.  Per-channel only (the reference's loader allows no sub-channel A8W8, model_loader.py:905-918)
+// and one input (no fused residual).
+class GemmA8W8HIP : public GemmLowpHIP<8> {
+ public:
+  explicit GemmA8W8HIP(const std::string& op_type = "") : GemmLowpHIP<8>(op_type) {}
+
+  AsStatus InitV2(const OperatorProto& op_proto, const DeviceContext& ctx, const TensorMap& weights_map, TensorMap& weights_buffer,
+                  TensorMap* tensor_map, RuntimeContext* runtime_ctx) override {
+    auto it = op_proto.attr.find("GroupSize");
+    if (it != op_proto.attr.end() && *(const int*)it->second.c_str() != -1) return AsStatus::ALLSPARK_PARAM_ERROR;
+    if (op_proto.inputs.size() != 1) return AsStatus::ALLSPARK_PARAM_ERROR;
+    return GemmLowpHIP<8>::InitV2(op_proto, ctx, weights_map, weights_buffer, tensor_map, runtime_ctx);
+  }
+
+  AsStatus Reshape(RuntimeContext* rt) override {
+    AS_CHECK_STATUS(GemmLowpHIP<8>::Reshape(rt));
+    // the larger of the two phases' needs: Forward only enqueues
+    const int64_t ws = (int64_t)dihip_gemm_a8w8_workspace_bytes(std::max(m_, 1), n_, k_);
+    if (ws == 0) return AsStatus::ALLSPARK_PARAM_ERROR;  // K beyond the int32 accumulator's range
+    AsTensor* wsp = tensor_map_->at("workspace").get();
+    if (wsp->GetSizeInByte() < (size_t)ws) AS_CHECK_STATUS(wsp->SetShape(Shape{ws}));
+    return AsStatus::ALLSPARK_SUCCESS;
+  }
+
+  AsStatus Forward(RuntimeContext* rt) override {
+    if (!rt || !rt->is_context) return GemmLowpHIP<8>::Forward(rt);
+    AsTensor* x = tensor_map_->at(in_names_[0]).get();
+    AsTensor* y = tensor_map_->at(out_names_[0]).get();
+    AsTensor* wsp = tensor_map_->at("workspace").get();
+    const void* bias = weights_.size() == 4 ? weights_[3]->GetDataPtr() : nullptr;
+    if (x->GetDataType() != ftype_) return AsStatus::ALLSPARK_PARAM_ERROR;
+    hipStream_t s = static_cast<const HIPContext*>(ctx_)->GetStream();
+    return FromDihip(dihip_gemm_a8w8(s, x->GetDataPtr(), packed_w_->GetDataPtr(), packed_sz_->GetDataPtr(), bias, nullptr, y->GetDataPtr(),
+                                     m_, n_, k_, (int)activation_, wsp->GetDataPtr(), wsp->GetSizeInByte(), DihipDtype(ftype_)));
+  }
+};
+REGISTER_OP(GemmA8W8, HIP, GemmA8W8HIP)
 
 }  // namespace allspark

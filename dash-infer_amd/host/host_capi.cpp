@@ -109,6 +109,16 @@ const char* dihost_registered_ops(void) {
   return s.c_str();
 }
 
+int dihost_op_registered(const char* op_type) {
+  if (!op_type || !*op_type) return 0;
+  try {
+    (void)OpFactory::getInstance().GetOperator({op_type, DeviceType::HIP});
+    return 1;
+  } catch (const AsException&) {
+    return 0;
+  }
+}
+
 int dihost_model_create(dihost_model_t* m, void* stream, int num_heads, int num_groups, int size_per_head, int span_size,
                         int cache_mode, int max_batch, int max_length, int rank, int nranks, void* rccl_comm) {
   if (!m) return (int)AsStatus::ALLSPARK_PARAM_ERROR;

@@ -52,6 +52,7 @@ _SIGS = {
     "dihost_requests_rewind": (i32, [vp, i32]),
     "dihost_last_error": (C.c_char_p, []),
     "dihost_registered_ops": (C.c_char_p, []),
+    "dihost_op_registered": (C.c_int, [C.c_char_p]),
 }
 _lib = None
 

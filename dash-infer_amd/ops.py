@@ -119,6 +119,110 @@ def fused_norm_gemm(h, gamma, eps, pw, bias, scratch, act=None, out=None):
     return y
 
 
+# ------------------------------------------------------------------- int8-activation GEMM (op GemmA8W8)
+class QuantizedAct:
+    """Activation rows quantised per row: q int8 [M, roundup(K, 64)] (zero beyond K), a_scale f32 [M], rsum i32 [M]."""
+
+    def __init__(self, q, a_scale, rsum, K):
+        self.q, self.a_scale, self.rsum, self.K = q, a_scale, rsum, K
+
+
+def a8w8_workspace_bytes(M, N, K):
+    return int(lib().dihip_gemm_a8w8_workspace_bytes(M, N, K))
+
+
+def _a8_alloc(M, K, device):
+    Kp = (K + 63) // 64 * 64
+    return QuantizedAct(torch.empty(max(M, 1), Kp, dtype=torch.int8, device=device)[:M], torch.empty(M, dtype=torch.float32, device=device),
+                        torch.empty(M, dtype=torch.int32, device=device), K)
+
+
+def act_quant_i8(x):
+    """x FT [M, K] (rows may be strided: ldx = x.stride(0)) -> QuantizedAct."""
+    M, K = x.shape
+    assert x.stride(1) == 1
+    qa = _a8_alloc(M, K, x.device)
+    check(lib().dihip_act_quant_i8(cur_stream(), ptr(x), x.stride(0) if M > 1 else max(x.stride(0), K), M, K, dt_code(x), ptr(qa.q),
+                                   ptr(qa.a_scale), ptr(qa.rsum)), "dihip_act_quant_i8")
+    return qa
+
+
+def norm_act_quant_i8(h, gamma, eps):
+    """h f32 [M, K] -> QuantizedAct of FT(RMSNorm(h) * gamma), FT = gamma's type."""
+    M, K = h.shape
+    qa = _a8_alloc(M, K, h.device)
+    ws = torch.empty(max(M * K * 2, 256), dtype=torch.uint8, device=h.device)
+    check(lib().dihip_norm_act_quant_i8(cur_stream(), ptr(h), ptr(gamma), float(eps), M, K, dt_code(gamma), ptr(qa.q), ptr(qa.a_scale),
+                                        ptr(qa.rsum), ptr(ws), ws.numel()), "dihip_norm_act_quant_i8")
+    return qa
+
+
+def gemm_a8w8_q(qa, pw, bias=None, residual=None, act=None, out=None):
+    """Quantised rows x packed int8 per-channel weight -> FT [M, N] (FT = the weight's scale type)."""
+    M = qa.q.shape[0]
+    y = out if out is not None else torch.empty(M, pw.N, dtype=pw.dtype, device=qa.q.device)
+    check(lib().dihip_gemm_a8w8_q(cur_stream(), ptr(qa.q), ptr(qa.a_scale), ptr(qa.rsum), ptr(pw.w), ptr(pw.sz), ptr(bias), ptr(residual),
+                                  ptr(y), M, pw.N, pw.K, capi.ACT[act], dt_code(pw.dtype)), "dihip_gemm_a8w8_q")
+    return y
+
+
+def gemm_a8w8_swiglu_q(qa, pg, pu, out=None):
+    M = qa.q.shape[0]
+    y = out if out is not None else torch.empty(M, pg.N, dtype=pg.dtype, device=qa.q.device)
+    check(lib().dihip_gemm_a8w8_swiglu_q(cur_stream(), ptr(qa.q), ptr(qa.a_scale), ptr(qa.rsum), ptr(pg.w), ptr(pg.sz), ptr(pu.w), ptr(pu.sz),
+                                         ptr(y), M, pg.N, pg.K, dt_code(pg.dtype)), "dihip_gemm_a8w8_swiglu_q")
+    return y
+
+
+def gemm_a8w8_addto_q(qa, pw, h_res, out=None):
+    M = qa.q.shape[0]
+    y = out if out is not None else torch.empty(M, pw.N, dtype=torch.float32, device=qa.q.device)
+    check(lib().dihip_gemm_a8w8_addto_q(cur_stream(), ptr(qa.q), ptr(qa.a_scale), ptr(qa.rsum), ptr(pw.w), ptr(pw.sz), ptr(h_res), ptr(y),
+                                        M, pw.N, pw.K, dt_code(pw.dtype)), "dihip_gemm_a8w8_addto_q")
+    return y
+
+
+def _a8_ws(ws, M, N, K, device):
+    return ws if ws is not None else torch.empty(max(a8w8_workspace_bytes(max(M, 1), N, K), 256), dtype=torch.uint8, device=device)
+
+
+def gemm_a8w8(x, pw, bias=None, residual=None, act=None, ws=None, out=None):
+    """op GemmA8W8, context phase: x FT [..., K] -> FT [..., N] (quantiser + int8 GEMM)."""
+    M = x.numel() // pw.K
+    y = out if out is not None else torch.empty(*x.shape[:-1], pw.N, dtype=x.dtype, device=x.device)
+    ws = _a8_ws(ws, M, pw.N, pw.K, x.device)
+    check(lib().dihip_gemm_a8w8(cur_stream(), ptr(x), ptr(pw.w), ptr(pw.sz), ptr(bias), ptr(residual), ptr(y), M, pw.N, pw.K,
+                                capi.ACT[act], ptr(ws), ws.numel(), dt_code(x)), "dihip_gemm_a8w8")
+    return y
+
+
+def a8w8_norm_gemm(h, gamma, eps, pw, bias=None, act=None, ws=None, out=None):
+    M = h.shape[0]
+    y = out if out is not None else torch.empty(M, pw.N, dtype=pw.dtype, device=h.device)
+    ws = _a8_ws(ws, M, pw.N, pw.K, h.device)
+    check(lib().dihip_a8w8_norm_gemm(cur_stream(), ptr(h), ptr(gamma), float(eps), ptr(pw.w), ptr(pw.sz), ptr(bias), ptr(y), M, pw.N, pw.K,
+                                     capi.ACT[act], ptr(ws), ws.numel(), dt_code(pw.dtype)), "dihip_a8w8_norm_gemm")
+    return y
+
+
+def a8w8_norm_swiglu(h, gamma, eps, pg, pu, ws=None, out=None):
+    M = h.shape[0]
+    y = out if out is not None else torch.empty(M, pg.N, dtype=pg.dtype, device=h.device)
+    ws = _a8_ws(ws, M, pg.N, pg.K, h.device)
+    check(lib().dihip_a8w8_norm_swiglu(cur_stream(), ptr(h), ptr(gamma), float(eps), ptr(pg.w), ptr(pg.sz), ptr(pu.w), ptr(pu.sz), ptr(y), M,
+                                       pg.N, pg.K, ptr(ws), ws.numel(), dt_code(pg.dtype)), "dihip_a8w8_norm_swiglu")
+    return y
+
+
+def a8w8_gemm_addto(x, pw, h_res, ws=None, out=None):
+    M = x.numel() // pw.K
+    y = out if out is not None else torch.empty(M, pw.N, dtype=torch.float32, device=x.device)
+    ws = _a8_ws(ws, M, pw.N, pw.K, x.device)
+    check(lib().dihip_a8w8_gemm_addto(cur_stream(), ptr(x), ptr(pw.w), ptr(pw.sz), ptr(h_res), ptr(y), M, pw.N, pw.K, ptr(ws), ws.numel(),
+                                      dt_code(x)), "dihip_a8w8_gemm_addto")
+    return y
+
+
 # ---------------------------------------------------------------------------- mixture of experts
 class PackedExperts:
     """num_experts equally shaped quantised matrices [K, N], each packed like PackedWeight, stacked back to back."""

@@ -4,11 +4,17 @@ plain tuples (op_type, op_name, inputs, outputs, weights, attrs): what bench.py'
 C++ operator layer (hostapi.Model.graph_build).  Pure Python: the CPU tests of the fusion pass use it without a GPU."""
 
 
-def qwen2_graph(n_layers, wbits, group, eps, n_heads, n_kv, rope_theta, tp_allreduce=False, tp_lm_head=False, moe=None):
-    """moe = (num_experts, top_k[, use_ep]): the feed-forward half of every layer is the mixture-of-experts block of
+def qwen2_graph(n_layers, wbits, group, eps, n_heads, n_kv, rope_theta, tp_allreduce=False, tp_lm_head=False, moe=None, act_quant=False):
+    """act_quant: the projections are GemmA8W8 (QuantMode.A8W8, quantization_utils.py:65-66: int8 per-channel weights, activations
+    quantised per row in the context phase), which has no GroupSize.
+    moe = (num_experts, top_k[, use_ep]): the feed-forward half of every layer is the mixture-of-experts block of
     python/pyhie/allspark/model/qwen_v20_moe.py:318-391 (MOE in its weight-only form MOEA16W8)."""
     gemm = "GemmA16W4" if wbits == 4 else "GemmA16W8"
     gattr = f"GroupSize=i:{group}" if group and group > 0 else ""
+    if act_quant:
+        if wbits != 8 or gattr:
+            raise ValueError("GemmA8W8 is int8 per-channel only")
+        gemm = "GemmA8W8"
 
     def lowp(name, inp, out, act=0, bias=False):
         w = [name + ".weight", name + ".weight.scale", name + ".weight.zero_point"] + ([name + ".bias"] if bias else [])

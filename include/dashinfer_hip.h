@@ -198,6 +198,54 @@ int dihip_prenorm_rowsq_supported(int wbits, int M, int N, int K, int group_size
 size_t dihip_rowsq_bytes(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1c. int8-activation GEMM for the context phase (replaces GemmA8W8GPU's int8 x int8 path,
+ *     csrc/core/operator/general/gemm_lowp/gemm_a8w8_gpu.cpp:119-210, and its kernels
+ *     per_channel_symm_dynamic_quantization / A_perc_symm_B_perc_asymm_dequantization,
+ *     csrc/core/kernel/cuda/gemm_lowp/gemm_a8w8_perc_kernel.cu:28-133, 400-469).
+ *     Weights: the packed image of dihip_gemm_lowp_pack(wbits 8), PER-CHANNEL only (group_size -1) -- the same
+ *     buffers dihip_gemm_a16w8 reads, so one copy serves the decoder phase (A16W8) and the context phase.
+ *     x FT [M, K] (bf16 / f16); every line ONE IEEE f32 operation per element, in this order:
+ *         amax = max_k |x[m,k]|;  a_scale = amax / 127;  rec = 127 / amax
+ *         q[m,k] = int8(rint(min(127, max(-128, x[m,k] * rec))))          (a row of zeros: q = 0, a_scale = 0)
+ *         rsum[m] = sum_k q[m,k];  acc = sum_k q[m,k] * Wq[k,n]          (int32, exact; K <= 131072, else PARAM_ERROR)
+ *         f = float(acc) - float(zero[n]) * float(rsum[m]);  f = f * (a_scale[m] * float(scale[n]));  f = f + bias[n]
+ *         y = FT(f);  with an activation: y = FT(act(float(y)));  with a residual: y = FT(float(y) + residual[m,n])
+ *     (alpha is not a parameter: the reference's A8W8 path ignores it).
+ *     xq: int8 [M, roundup(K, 64)] row-major, zero beyond K, 16-byte aligned; a_scale f32 [M]; rsum i32 [M].
+ *     dihip_gemm_a8w8_workspace_bytes: xq + a_scale + rsum (+ FT rows for the widths dihip_norm_act_quant_i8 serves in two
+ *     launches); 0 for an empty or invalid shape.  The workspace is 16-byte aligned.  No call allocates or synchronises. */
+size_t dihip_gemm_a8w8_workspace_bytes(int M, int N, int K);
+int dihip_act_quant_i8(void* stream, const void* x, int ldx, int M, int K, int dtype, void* xq, float* a_scale,
+                       int* rsum);
+/* ... of FT(RMSNorm(h) * gamma), h f32 [M, K]: the rows dihip_rmsnorm_rows writes (same bits), quantised in the same
+ * launch for K % 4 == 0, K <= 8192; other widths: dihip_rmsnorm_rows into ws (M * K * 2 bytes) + dihip_act_quant_i8 */
+int dihip_norm_act_quant_i8(void* stream, const float* h, const void* gamma, float eps, int M, int K, int dtype,
+                            void* xq, float* a_scale, int* rsum, void* ws, size_t ws_bytes);
+/* GEMM over rows quantised by the calls above: STD epilogue; SwiGLU over a gate / up pair sharing one quantised A,
+ * y = FT(FT(SiLU(FT(gate))) * FT(up)) (GemmA8W8(SILU), GemmA8W8, Binary MUL); h_out = h_res + f on the f32 hidden
+ * stream (h_res may be NULL) */
+int dihip_gemm_a8w8_q(void* stream, const void* xq, const float* a_scale, const int* rsum, const void* w_packed,
+                      const void* sz_packed, const void* bias, const void* residual, void* y, int M, int N, int K,
+                      int act, int dtype);
+int dihip_gemm_a8w8_swiglu_q(void* stream, const void* xq, const float* a_scale, const int* rsum,
+                             const void* wg_packed, const void* szg_packed, const void* wu_packed,
+                             const void* szu_packed, void* y, int M, int N, int K, int dtype);
+int dihip_gemm_a8w8_addto_q(void* stream, const void* xq, const float* a_scale, const int* rsum, const void* w_packed,
+                            const void* sz_packed, const float* h_res, float* h_out, int M, int N, int K, int dtype);
+/* quantise + GEMM (two launches), the quantised rows in ws; siblings of dihip_fused_norm_gemm, dihip_fused_norm_swiglu
+ * and dihip_fused_gemm_addto for the context phase */
+int dihip_gemm_a8w8(void* stream, const void* x, const void* w_packed, const void* sz_packed, const void* bias,
+                    const void* residual, void* y, int M, int N, int K, int act, void* ws, size_t ws_bytes, int dtype);
+int dihip_a8w8_norm_gemm(void* stream, const float* h, const void* gamma, float eps, const void* w_packed,
+                         const void* sz_packed, const void* bias, void* y, int M, int N, int K, int act, void* ws,
+                         size_t ws_bytes, int dtype);
+int dihip_a8w8_norm_swiglu(void* stream, const float* h, const void* gamma, float eps, const void* wg_packed,
+                           const void* szg_packed, const void* wu_packed, const void* szu_packed, void* y, int M, int N,
+                           int K, void* ws, size_t ws_bytes, int dtype);
+int dihip_a8w8_gemm_addto(void* stream, const void* x, const void* w_packed, const void* sz_packed,
+                          const float* h_res, float* h_out, int M, int N, int K, void* ws, size_t ws_bytes, int dtype);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b. Mixture-of-experts decode path with weight-only experts (BASELINE configs[4]).
  *     Semantics of the reference's MOE operator (csrc/core/operator/general/moe/moe_op.cpp:338-460): float
  *     softmax of the router logits, top-k WITHOUT renormalisation, per (token, expert) SiLU(x.Wgate) * (x.Wup)

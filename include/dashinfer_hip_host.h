@@ -135,6 +135,8 @@ int dihost_requests_rewind(dihost_model_t m, int cached_len);
 const char* dihost_last_error(void);
 /* "GemmA16W8,GemmA16W4,DecOptMHA,DecOptMQA,AllReduce": op types registered for DeviceType::HIP */
 const char* dihost_registered_ops(void);
+/* 1 when `op_type` is registered on DeviceType::HIP (any type, not only the ones the list above probes), else 0 */
+int dihost_op_registered(const char* op_type);
 #ifdef __cplusplus
 }
 #endif
