@@ -156,6 +156,7 @@ _SIGS = {
     "dihip_debug_attn_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
     "dihip_debug_gemv_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
                               C.POINTER(sz)]),
+    "dihip_debug_gemm_route": (i32, [i32] * 11 + [C.POINTER(C.c_longlong)]),
 }
 
 _lib = None

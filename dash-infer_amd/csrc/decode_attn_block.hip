@@ -37,11 +37,11 @@
 #include <unordered_map>
 
 #include "gemv_stream_kernel.hpp"
+#include "gemm_lowp_plan.hpp"
 #include "span_attn_ft_mfma.hpp"
 
 namespace dihip {
 
-bool gemv_block_plan(int wbits, int N, int K, int group_size, int nblocks, GemvArgs* g, int* max_units, size_t* lds_bytes);
 void span_attn_block_plan(int batch, int n_heads, int n_groups, int max_seq_len, int* nsplits, int* nchunks, int* tps_static,
                           size_t* partial_bytes, int* waves);
 

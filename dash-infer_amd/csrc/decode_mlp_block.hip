@@ -18,10 +18,9 @@
 #include <cstdlib>
 
 #include "gemv_stream_kernel.hpp"
+#include "gemm_lowp_plan.hpp"
 
 namespace dihip {
-
-bool gemv_plan_args(int wbits, int N, int K, int group_size, bool dual, GemvArgs* g, int* blocks, size_t* lds_bytes);
 
 struct MlpBlockArgs {
   GemvArgs gu;    // RMSNorm + gate / up + SwiGLU

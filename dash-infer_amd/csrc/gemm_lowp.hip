@@ -1,10 +1,8 @@
-// gemm_lowp.hip -- C-ABI entry points, weight re-layout and launch heuristics of the
-// weight-only GEMM (include/dashinfer_hip.h section 1).
+// gemm_lowp.hip -- weight re-layout kernels, kernel launch and the C-ABI entry points of the weight-only GEMM
+// (include/dashinfer_hip.h section 1).  Which kernel serves a call, and with which grid: gemm_lowp_plan.hpp.
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 
+#include "gemm_lowp_plan.hpp"
 #include "gemm_lowp_launch.hpp"
 #include "gemv_stream_kernel.hpp"
 #include "gemm_prefill_kernel.hpp"
@@ -25,24 +23,6 @@ namespace dihip {
 //   a weight chunk are 64 contiguous bytes, consecutive groups of a tile are adjacent), lo16 =
 //   scale bits, hi16 = zero bits (FT), zero padded; Gp = max(G, ceil(Kp / group)).
 // ------------------------------------------------------------------------------------------
-static inline int roundup(int v, int m) { return (v + m - 1) / m * m; }
-
-struct LowpDims {
-  int KTILE, Kp, KT, Np, NTILES, G, Gp, group;
-};
-static LowpDims lowp_dims(int wbits, int N, int K, int group_size) {
-  LowpDims d;
-  d.KTILE = wbits == 4 ? 128 : wbits == 8 ? 64 : 32;
-  d.Kp = roundup(K, d.KTILE);
-  d.KT = d.Kp / d.KTILE;
-  d.Np = roundup(N, 16);
-  d.NTILES = d.Np / 16;
-  d.group = group_size > 0 ? group_size : 0;
-  d.G = d.group ? (K + d.group - 1) / d.group : 1;
-  d.Gp = d.group ? std::max(d.G, (d.Kp + d.group - 1) / d.group) : 1;
-  return d;
-}
-
 __global__ void pack_w4_kernel(const uint8_t* __restrict__ wq, uint32_t* __restrict__ out, int N,
                                int K, int KT, int NTILES) {
   const size_t total = (size_t)NTILES * KT * 64 * 4;
@@ -128,887 +108,6 @@ __global__ void pack_sz_kernel(const uint16_t* __restrict__ s, const uint16_t* _
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// launch plan
-// ------------------------------------------------------------------------------------------
-struct GemmPlan {
-  int MT, NT, NTW, col_blocks, m_blocks, splitk, ktiles_per_split, kslice_tiles;
-  size_t lds_bytes, slab_bytes;
-};
-
-static GemmPlan make_plan(int wbits, int M, int N, int K, int group_size, bool dual) {
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  GemmPlan p;
-  p.MT = M > 16 ? 2 : 1;
-  const int rows_per_block = 16 * p.MT;
-  p.m_blocks = (M + rows_per_block - 1) / rows_per_block;
-  const int num_cus = cached_num_cus();
-  const int target_blocks = num_cus > 0 ? (num_cus * 5) / 2 : 640;
-  // tiles per wave: 4 streams/wave normally; 2 when the matrix is too narrow to fill the chip
-  p.NT = 4;
-  if (!dual && wbits != 16) {
-    const int cb4 = (d.NTILES + GEMM_WAVES * 4 - 1) / (GEMM_WAVES * 4);
-    if ((long)cb4 * p.m_blocks * d.KT < target_blocks) p.NT = 2;
-  }
-  p.NTW = dual ? p.NT / 2 : p.NT;
-  p.col_blocks = (d.NTILES + GEMM_WAVES * p.NTW - 1) / (GEMM_WAVES * p.NTW);
-  // split-K granule: whole quantisation groups, whole k-tiles
-  int granule = 1;
-  if (d.group > d.KTILE) granule = (d.group + d.KTILE - 1) / d.KTILE;
-  const int units = (d.KT + granule - 1) / granule;
-  int want = (int)std::max<long>(1, target_blocks / std::max<long>(1, (long)p.col_blocks * p.m_blocks));
-  want = std::min(want, units);
-  // a skinny unquantised matrix (the MoE router, hidden -> 64 experts; the shared expert's gate, hidden -> 1) is ONE column block:
-  // its last-arriving workgroup sums every split's partial tile alone -- 112 splits of one k-tile took 19.8 us (profiles/r03u),
-  // most of it that serial sum
-  if (wbits == 16 && (long)p.col_blocks * p.m_blocks <= 2) want = std::min(want, 16);
-  int units_per_split = (units + want - 1) / want;
-  p.ktiles_per_split = units_per_split * granule;
-  p.splitk = (d.KT + p.ktiles_per_split - 1) / p.ktiles_per_split;
-  // the activation slice is staged in LDS in pieces of at most ~60 KiB:
-  // (rows+1) * (kslice*KTILE + 8) * 2 bytes
-  const int rows = std::min(M, rows_per_block);
-  const int max_tiles = std::max(1, (60 * 1024 / ((rows + 1) * 2) - 8) / d.KTILE);
-  // several slices: each a multiple of the register ring depth (gemm_lowp_kernel.hpp)
-  p.kslice_tiles = p.ktiles_per_split <= max_tiles ? p.ktiles_per_split : std::max(GEMM_RING, max_tiles / GEMM_RING * GEMM_RING);
-  p.lds_bytes = GEMM_LDS_HEADER + (size_t)(rows + 1) * (p.kslice_tiles * d.KTILE + 8) * 2;
-  p.slab_bytes = p.splitk > 1 ? (size_t)p.splitk * M * (dual ? 2 : 1) * d.Np * sizeof(float) : 0;
-  return p;
-}
-
-constexpr size_t GEMM_SYNC_BYTES = 64 * 1024;  // up to 16384 (column-block x m-block) counters
-
-template <int WBITS, int FT>
-static hipError_t dispatch(const GemmPlan& p, int pro, int epi, const GemmArgs& a, dim3 grid,
-                           hipStream_t s) {
-#define CASE(MT_, NT_, PRO_, EPI_)                                                 \
-  if (p.MT == MT_ && p.NT == NT_ && pro == PRO_ && epi == EPI_)                    \
-    return launch_gemm_lowp<WBITS, FT, MT_, NT_, PRO_, EPI_>(a, grid, p.lds_bytes, s);
-  CASE(1, 2, PRO_PLAIN, EPI_STD)
-  CASE(1, 4, PRO_PLAIN, EPI_STD)
-  CASE(2, 2, PRO_PLAIN, EPI_STD)
-  CASE(2, 4, PRO_PLAIN, EPI_STD)
-  {  // fused decode-step forms: bf16 and (round 4) f16
-    CASE(1, 2, PRO_RMSNORM, EPI_STD)
-    CASE(1, 4, PRO_RMSNORM, EPI_STD)
-    CASE(1, 4, PRO_RMSNORM, EPI_SWIGLU)
-    CASE(1, 4, PRO_PLAIN, EPI_SWIGLU)
-    CASE(2, 4, PRO_PLAIN, EPI_SWIGLU)
-    CASE(1, 2, PRO_PLAIN, EPI_ADDTO)
-    CASE(1, 4, PRO_PLAIN, EPI_ADDTO)
-    CASE(2, 2, PRO_PLAIN, EPI_ADDTO)
-    CASE(2, 4, PRO_PLAIN, EPI_ADDTO)
-  }
-#undef CASE
-  return hipErrorInvalidValue;
-}
-
-template <int FT>
-static hipError_t dispatch_dense(const GemmPlan& p, int pro, int epi, const GemmArgs& a, dim3 grid, hipStream_t s) {
-#define CASE(MT_, PRO_, EPI_)                                   \
-  if (p.MT == MT_ && p.NT == 4 && pro == PRO_ && epi == EPI_)   \
-    return launch_gemm_lowp<16, FT, MT_, 4, PRO_, EPI_>(a, grid, p.lds_bytes, s);
-  CASE(1, PRO_RMSNORM, EPI_ADDTO)
-  CASE(1, PRO_PLAIN, EPI_ADDTO)
-  CASE(2, PRO_PLAIN, EPI_ADDTO)
-  CASE(1, PRO_PLAIN, EPI_STD)
-  CASE(2, PRO_PLAIN, EPI_STD)
-#undef CASE
-  return hipErrorInvalidValue;
-}
-
-struct GemmCall {
-  int wbits, dtype, pro, epi;
-  const void* x;
-  int ldx;
-  const void* gamma;
-  float eps;
-  const void *w0, *sz0, *w1, *sz1;
-  const void *bias, *residual;
-  void* y;
-  const float* h_res;
-  float* h_out;
-  int M, N, K, group_size, act;
-  float alpha;
-  void* ws;
-  size_t ws_bytes;
-  void* sync;
-  int x_layout, y_layout;  // DIHIP_ACT_ROWMAJOR / DIHIP_ACT_FRAG32 (small-batch kernel only)
-  // EPI_ADDTO: RMSNorm of the finished rows wanted in n_out (dihip_fused_gemm_addto_norm); *n_done is set when the kernel
-  // family that served the call has produced it (split-K slab reduction), otherwise the caller runs the norm kernel
-  const void* n_gamma;
-  float n_eps;
-  void* n_out;
-  int n_frag_mt;
-  bool* n_done;
-  // deferred RMSNorm (gemv_batch_kernel.hpp, GembArgs).  Producer: n_rowsq != null asks for n_out = FT(gamma * h_out) and the
-  // row partials instead of the finished norm; *n_parts = parts written, 0 when the serving kernel does not offer it (the
-  // norm is then produced as above).  Consumer: rowsq != null -- rows are scaled by 1 / rms on the accumulator.
-  float* n_rowsq;
-  size_t n_rowsq_bytes;
-  int* n_parts;
-  const float* rowsq;
-  int rowsq_parts;
-  float rowsq_eps;
-};
-
-
-// ---- decode fast path (gemv_stream_kernel.hpp) ------------------------------------------------
-struct GemvPlan {
-  bool ok;
-  int MR, upb, blocks, WK, WN, ktpg, kgroups, RS;
-  size_t lds_bytes;
-};
-
-// K-slice boundaries of a plan (GemvArgs::kcut) and the wave mapping.  Even split: kcut[i] = kgroups * i / WK (the former
-// in-kernel formula).  DIHIP_GEMV_KSKEW = s (per cent): the k-slices held by the first-dispatched half of the workgroup's waves
-// get (1 + s/100) shares, the others (1 - s/100) -- the two waves of a SIMD are arbitrated by age and the younger half streams
-// ~13 % slower (profiles/r03_gemv_wave_timeline.txt); boundaries rounded to whole split units, every slice keeps >= 1 unit when
-// there are enough.  DIHIP_GEMV_WMAP = 1: consecutive waves differ in wn, so that the k-slices ARE ordered by age also for the
-// WK 4 x WN 2 plans (gate / up pair: without it waves 0-3 stream the gate matrix and 4-7 the up matrix, and no K split can
-// balance them).
-static void fill_kcut(GemvArgs& g) {
-  static const int skew = std::max(0, std::min(60, env_int("DIHIP_GEMV_KSKEW", 0)));
-  static const int wmap_env = env_int("DIHIP_GEMV_WMAP", 0);
-  g.wmap = (wmap_env && g.WN > 1 && g.WK > 1) ? 1 : 0;
-  const int WK = g.WK, G = g.kgroups;
-  // which k-slices sit on the older half of the waves
-  auto older = [&](int wk) {
-    if (WK == 1) return true;
-    if (g.WN == 1) return wk < WK / 2;           // wave == wk
-    return g.wmap ? wk < WK / 2 : true;           // wmap 0 with WN > 1: every k-slice has waves of both halves
-  };
-  const bool skewed = skew > 0 && (g.WN == 1 || g.wmap) && WK >= 2 && G >= 2 * WK;
-  double tot = 0;
-  double w[GEMV_WAVES];
-  for (int i = 0; i < WK; ++i) {
-    w[i] = skewed ? (older(i) ? 100.0 + skew : 100.0 - skew) : 100.0;
-    tot += w[i];
-  }
-  g.kcut[0] = 0;
-  double acc = 0;
-  for (int i = 0; i < WK; ++i) {
-    acc += w[i];
-    int c = skewed ? (int)(G * acc / tot + 0.5) : (int)(((long)G * (i + 1)) / WK);
-    c = std::max(c, g.kcut[i]);
-    g.kcut[i + 1] = std::min(c, G);
-  }
-  g.kcut[WK] = G;
-  for (int i = WK + 1; i <= GEMV_WAVES; ++i) g.kcut[i] = G;
-}
-
-// want_blocks > 0 (expert slots: gridDim.y multiplies the grid): aim at that many workgroups instead of one per CU
-static GemvPlan make_gemv_plan(int wbits, int M, int N, int K, int group_size, bool dual, int want_blocks = 0) {
-  GemvPlan p{};
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  p.ok = false;
-  // DIHIP_GEMV_STREAM_MAXM: largest batch served by the LDS-resident kernel (beyond 4 rows the per-workgroup x staging, M x K
-  // into LDS, costs more than the small-batch kernel)
-  static const int max_m = std::max(1, std::min(16, env_int("DIHIP_GEMV_STREAM_MAXM", 4)));
-  if (M < 1 || M > max_m) return p;
-  if (d.group && d.group % d.KTILE != 0) return p;  // groups smaller than a k-tile: general kernel
-  p.ktpg = d.group ? d.group / d.KTILE : (1 << 28);
-  p.MR = M == 1 ? 1 : 4;
-  p.RS = d.Kp + 8;
-  int num_cus = cached_num_cus();
-  if (num_cus <= 0) num_cus = 256;
-  const int units = d.NTILES;
-  // never more workgroups than CUs (a second round starts ~2 us late, measured on the qkv shape):
-  // one tile per workgroup up to the CU count, ceil(tiles / CUs) beyond
-  p.upb = units <= num_cus ? 1 : (units + num_cus - 1) / num_cus;
-  static const int upb_override = env_int("DIHIP_GEMV_UPB", 0);  // experiments: units per workgroup for the multi-unit shapes
-  if (upb_override > 0 && p.upb > 1) p.upb = upb_override;
-  static const int upb_small = env_int("DIHIP_GEMV_UPB_SMALL", 0);  // experiments: units per workgroup for shapes with units in (CUs, 1.5 CUs]
-  if (upb_small > 0 && p.upb == 1 && units > num_cus) p.upb = upb_small;
-  if (want_blocks > 0) p.upb = std::max(1, (units + want_blocks - 1) / want_blocks);
-  p.blocks = (units + p.upb - 1) / p.upb;
-  const int nv = p.upb * (dual ? 2 : 1);
-  const int kgroups = d.group ? (d.KT + p.ktpg - 1) / p.ktpg : d.KT;
-  // wave grid WK x WN: minimise the longest per-wave chunk sequence (ties: fewer k-slices)
-  long best = -1;
-  p.kgroups = kgroups;
-  for (int wn = GEMV_WAVES; wn >= (dual ? 2 : 1); wn /= 2) {
-    const int wkk = GEMV_WAVES / wn;
-    if (wkk > kgroups) continue;
-    const long load = (long)((nv + wn - 1) / wn) * ((kgroups + wkk - 1) / wkk);
-    if (best < 0 || load < best) {
-      best = load;
-      p.WN = wn;
-      p.WK = wkk;
-    }
-  }
-  if (best < 0) {
-    p.WN = GEMV_WAVES;
-    p.WK = 1;
-  }
-  p.lds_bytes = gemv_lds_bytes(M, p.RS, d.KT, p.upb, dual, p.WK);
-  if (p.lds_bytes > 150 * 1024) return p;
-  p.ok = true;
-  return p;
-}
-
-// The decode GEMV's plan for ONE row as the workgroups of ANOTHER launch run it (decode_attn_block.hip): the K split (WK, kcut)
-// and the wave grid are those of the stand-alone launch -- the sums are then bit-identical to it -- while the column tiles are dealt
-// over `nblocks` workgroups (block b owns tiles b, b + nblocks, ...).  Fills the shape / plan fields of *g (pointers are the
-// caller's); *max_units = most tiles one workgroup owns, *lds_bytes = its LDS need.  False: shape not served by the decode GEMV.
-bool gemv_block_plan(int wbits, int N, int K, int group_size, int nblocks, GemvArgs* g, int* max_units, size_t* lds_bytes) {
-  const GemvPlan gp = make_gemv_plan(wbits, 1, N, K, group_size, false);
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  if (!gp.ok || gp.MR != 1 || K != d.Kp || nblocks < 1 || nblocks > d.NTILES) return false;
-  g->M = 1;
-  g->N = N;
-  g->K = K;
-  g->ldx = K;
-  g->ldy = N;
-  g->KT = d.KT;
-  g->NTILES = d.NTILES;
-  g->Gp = lowp_dims(4, N, K, group_size).Gp;
-  g->ktpg = gp.ktpg;
-  g->kgroups = gp.kgroups;
-  g->WK = gp.WK;
-  g->WN = gp.WN;
-  g->RS = gp.RS;
-  g->nu_q = d.NTILES / nblocks;
-  g->nu_r = d.NTILES % nblocks;
-  g->upb = g->nu_q + (g->nu_r ? 1 : 0);
-  g->alpha = 1.f;
-  g->act = DIHIP_ACT_NONE;
-  fill_kcut(*g);
-  *max_units = g->upb;
-  *lds_bytes = gemv_lds_bytes(1, gp.RS, d.KT, g->upb, 0, gp.WK);
-  return true;
-}
-
-// The stand-alone decode GEMV's plan and shape fields for one row, as run_gemm fills them (decode_mlp_block.hip runs the bodies of
-// two such launches inside one: same blocks, same K split, same sums).  Pointers are the caller's.
-bool gemv_plan_args(int wbits, int N, int K, int group_size, bool dual, GemvArgs* g, int* blocks, size_t* lds_bytes) {
-  const GemvPlan gp = make_gemv_plan(wbits, 1, N, K, group_size, dual);
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  if (!gp.ok || gp.MR != 1 || K != d.Kp) return false;
-  g->M = 1;
-  g->N = N;
-  g->K = K;
-  g->ldx = K;
-  g->ldy = N;
-  g->KT = d.KT;
-  g->NTILES = d.NTILES;
-  g->Gp = lowp_dims(4, N, K, group_size).Gp;
-  g->ktpg = gp.ktpg;
-  g->kgroups = gp.kgroups;
-  g->upb = gp.upb;
-  g->nu_q = d.NTILES / gp.blocks;
-  g->nu_r = d.NTILES % gp.blocks;
-  g->WK = gp.WK;
-  g->WN = gp.WN;
-  g->RS = gp.RS;
-  g->alpha = 1.f;
-  g->act = DIHIP_ACT_NONE;
-  fill_kcut(*g);
-  *blocks = gp.blocks;
-  *lds_bytes = gp.lds_bytes;
-  return true;
-}
-
-template <int WBITS, int FT>
-static hipError_t dispatch_gemv(const GemvPlan& p, int pro, int epi, const GemvArgs& a, hipStream_t s) {
-  const bool gpt = WBITS != 16 && p.ktpg == 1;
-#define CASE(MR_, PRO_, EPI_)                                                              \
-  if (p.MR == MR_ && pro == PRO_ && epi == EPI_) {                                         \
-    if constexpr (WBITS != 16) {                                                           \
-      if (gpt) return launch_gemv_stream<WBITS, FT, MR_, PRO_, EPI_, 1>(a, p.blocks, p.lds_bytes, s); \
-    }                                                                                      \
-    return launch_gemv_stream<WBITS, FT, MR_, PRO_, EPI_, 0>(a, p.blocks, p.lds_bytes, s); \
-  }
-  CASE(1, PRO_PLAIN, EPI_STD)
-  CASE(4, PRO_PLAIN, EPI_STD)
-  CASE(1, PRO_RMSNORM, EPI_STD)
-  CASE(4, PRO_RMSNORM, EPI_STD)
-  CASE(1, PRO_RMSNORM, EPI_SWIGLU)
-  CASE(4, PRO_RMSNORM, EPI_SWIGLU)
-  CASE(1, PRO_PLAIN, EPI_SWIGLU)
-  CASE(4, PRO_PLAIN, EPI_SWIGLU)
-  CASE(1, PRO_PLAIN, EPI_ADDTO)
-  CASE(4, PRO_PLAIN, EPI_ADDTO)
-  CASE(1, PRO_RMSNORM, EPI_ADDTO)
-  CASE(4, PRO_RMSNORM, EPI_ADDTO)
-#undef CASE
-  return hipErrorInvalidValue;
-}
-
-// (round 3: f16 activations had the op-boundary form only; round 4 instantiates every form for f16 -- dispatch_gemv<WBITS, DIHIP_F16>)
-template <int WBITS>
-[[maybe_unused]] static hipError_t dispatch_gemv_f16(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
-  const bool gpt = p.ktpg == 1;
-  if (p.MR == 1) return gpt ? launch_gemv_stream<WBITS, DIHIP_F16, 1, PRO_PLAIN, EPI_STD, 1>(a, p.blocks, p.lds_bytes, s)
-                            : launch_gemv_stream<WBITS, DIHIP_F16, 1, PRO_PLAIN, EPI_STD, 0>(a, p.blocks, p.lds_bytes, s);
-  return gpt ? launch_gemv_stream<WBITS, DIHIP_F16, 4, PRO_PLAIN, EPI_STD, 1>(a, p.blocks, p.lds_bytes, s)
-             : launch_gemv_stream<WBITS, DIHIP_F16, 4, PRO_PLAIN, EPI_STD, 0>(a, p.blocks, p.lds_bytes, s);
-}
-
-static bool gemv_stream_enabled() {  // DIHIP_GEMV_STREAM=0 routes everything to the general kernel
-  static const bool on = !env_off("DIHIP_GEMV_STREAM");
-  return on;
-}
-
-// ---- batched decode, FRAG32 activations (gemm_panel_kernel.hpp) ----------------------------------------
-struct PanelPlan {
-  bool ok;
-  int panels, nslices, ktps;
-  size_t slab_bytes;
-};
-
-static PanelPlan make_panel_plan(int wbits, int M, int N, int K, int group_size, bool dual) {
-  PanelPlan p{};
-  static const bool enabled = !env_off("DIHIP_GEMM_PANEL");  // =0: keep the whole-column kernel (diagnostics)
-  if (!enabled) return p;
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  int ncu = cached_num_cus();
-  if (ncu <= 0) ncu = 256;
-  p.panels = (d.NTILES + PANEL_WAVES - 1) / PANEL_WAVES;
-  const int ktpg = d.group ? std::max(1, d.group / d.KTILE) : 1;  // slices hold whole quantisation groups
-  static const int target = env_int("DIHIP_PANEL_TARGET_WGS", 0), one_frac = env_int("DIHIP_PANEL_ONE_SLICE_PCT", 50);  // diagnostics
-  const int tgt = target > 0 ? target : ncu;
-  if (100 * p.panels >= one_frac * ncu) {
-    p.nslices = 1;  // enough panels to keep the HBM queue full from every second CU on
-    p.ktps = d.KT;
-  } else {
-    // few columns: split K so that about one workgroup lands on every CU, but keep >= 8 k-tiles per slice
-    int s = std::max(1, tgt / p.panels);
-    int ktps = (d.KT + s - 1) / s;
-    ktps = (ktps + ktpg - 1) / ktpg * ktpg;
-    if (ktps < 8) return p;  // the ring would never fill: the whole-column kernel handles these
-    p.ktps = ktps;
-    p.nslices = (d.KT + ktps - 1) / ktps;
-  }
-  p.slab_bytes = p.nslices > 1 ? (size_t)p.nslices * (dual ? 2 : 1) * M * N * sizeof(float) : 0;
-  p.ok = true;
-  return p;
-}
-
-// ---- batched decode, FRAG32 activations, register-resident K-slices (gemm_kslice_kernel.hpp) ---------------------
-// Context-phase GEMM, tail split (gemm_prefill_kernel.hpp, PrefillArgs::tail_cb): when the grid of 128 x 256 tiles ends in a
-// round that fills at most half the chip, the column blocks of that round are split in K instead -- `ksplit` workgroups per
-// tile, whole quantisation groups each, all of them within one round -- and a reduction launch adds the parts.  Qwen2-7B at
-// 2048 rows: qkv 288 tiles -> 256 + 32 x 7 parts (176 -> ~115 us), gate / up 2368 -> 2304 + 64 x 4.  DIHIP_PREFILL_TAIL_SPLIT=0: off.
-struct PrefillTail {
-  int col_blocks, mblocks, tail_cb, ksplit;
-  size_t slab_bytes;
-};
-static PrefillTail prefill_tail_plan(int wbits, int M, int N, int K, int group_size, bool dual) {
-  PrefillTail t{};
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  const int tpb = dual ? PF_WN * PF_CW / 2 : PF_WN * PF_CW;
-  t.col_blocks = (d.NTILES + tpb - 1) / tpb;
-  t.mblocks = (M + PF_BM - 1) / PF_BM;
-  t.tail_cb = t.col_blocks;
-  t.ksplit = 1;
-  static const bool on = !env_off("DIHIP_PREFILL_TAIL_SPLIT");
-  int ncu = cached_num_cus();
-  if (ncu <= 0) ncu = 256;
-  const int blocks = t.col_blocks * t.mblocks, rem = blocks % ncu;
-  if (!on || M < 64 || (wbits != 4 && wbits != 8) || blocks <= ncu || rem == 0 || rem > ncu / 2) return t;
-  const int tcb = (rem + t.mblocks - 1) / t.mblocks, tiles = tcb * t.mblocks;
-  if (tiles > ncu / 2 || tcb >= t.col_blocks) return t;
-  const int ktpg = d.group ? d.group / d.KTILE : d.KT;
-  const int units = d.group ? d.KT / std::max(ktpg, 1) : d.KT;  // K parts hold whole groups (per-channel: whole k-tiles)
-  int best = 1;
-  for (int ks = 2; ks <= 8; ++ks)
-    if (units % ks == 0 && tiles * ks <= ncu) best = ks;
-  if (best == 1) return t;
-  t.tail_cb = t.col_blocks - tcb;
-  t.ksplit = best;
-  t.slab_bytes = (size_t)tiles * best * PF_BM * 256 * sizeof(float);
-  return t;
-}
-
-struct KslicePlan {
-  bool ok;
-  int groups, nslices, waves, nunits;
-  size_t slab_bytes;
-};
-static KslicePlan make_kslice_plan(int wbits, int M, int N, int K, int group_size, bool dual, bool sizing = false) {
-  KslicePlan p{};
-  // DIHIP_GEMM_KSLICE: 0 = never, 2 = every eligible shape (tests / diagnostics); read per call so that one process can
-  // exercise both kernels
-  const char* e = getenv("DIHIP_GEMM_KSLICE");
-  const int mode = sizing ? 2 : e ? atoi(e) : 1;  // workspace sizing covers the forced mode as well
-  if (mode == 0 || (wbits != 4 && wbits != 8)) return p;
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  const int ch = wbits == 4 ? 4 : 8;  // k-tiles per K-slice (16 k-steps of 32)
-  if (d.KT % ch) return p;            // slices hold whole k-tiles of equal count
-  if (wbits == 8 && d.group == d.KTILE) return p;  // W8 g64 (a scale per k-tile in a 16-slot ring) does not fit the register file
-  // Measured against the panel kernel (tools/gemv_bench and bench.py, 7B and 72B/TP8 shapes): +13 % on the SwiGLU pair
-  // at M = 16 (8 KiB in flight per wave), +4 % (gate/up) and +8 % (down, split-K slab) at M = 32, but 30-40 % slower on
-  // matrices of a few MB (one or two half-units per workgroup: the ring never reaches steady state)
-  if (mode != 2 && (size_t)N * K * wbits / 8 * (dual ? 2 : 1) < ((size_t)24 << 20)) return p;
-  int ncu = cached_num_cus();
-  if (ncu <= 0) ncu = 256;
-  const int nsl = d.KT / ch;
-  p.waves = std::min(KSL_WAVES, nsl);
-  p.nslices = (nsl + KSL_WAVES - 1) / KSL_WAVES;
-  p.nunits = d.NTILES;
-  static const int target = env_int("DIHIP_KSLICE_TARGET_WGS", 0);  // diagnostics
-  const int tgt = target > 0 ? target : ncu;  // one 8-wave workgroup per CU (64 KB LDS, ~250 registers)
-  p.groups = std::max(1, std::min(p.nunits, tgt / p.nslices));
-  p.slab_bytes = p.nslices > 1 ? (size_t)p.nslices * (dual ? 2 : 1) * M * N * sizeof(float) : 0;
-  p.ok = true;
-  return p;
-}
-
-// One launch of M = 1 GEMVs over (token, expert-rank) slots (mixture-of-experts, moe.hip): slot s streams expert
-// slot_expert[s] of a stack of equally shaped packed weights, reads activation row s / x_div, writes row s.
-int run_gemv_slots(hipStream_t stream, int wbits, int epi, const void* x, int ldx, int x_div, const void* w0, const void* sz0,
-                   const void* w1, const void* sz1, void* y, int N, int K, int group_size, const int* slot_expert, int nslots,
-                   const int* group_rows, const int* group_nrows) {
-  const bool grouped = group_rows != nullptr;  // slot_expert / nslots then enumerate groups of <= 4 slots (moe.hip)
-  const bool dual = epi == EPI_SWIGLU;
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  DIHIP_REQUIRE(K == d.Kp && (d.group == 0 || d.group % d.KTILE == 0), DIHIP_PARAM_ERROR,
-                "moe: K = %d must be a multiple of the k-tile (%d) and groups whole k-tiles", K, d.KTILE);
-  // slots multiply the grid: about one workgroup per CU over the whole launch, at most 8 units per workgroup
-  int ncu = cached_num_cus();
-  if (ncu <= 0) ncu = 256;
-  const int want = std::max((d.NTILES + 7) / 8, (ncu + nslots - 1) / nslots);
-  const GemvPlan gp = make_gemv_plan(wbits, grouped ? 4 : 1, N, K, group_size, dual, want);
-  DIHIP_REQUIRE(gp.ok && gp.lds_bytes <= 64 * 1024, DIHIP_PARAM_ERROR, "moe: unsupported expert shape N=%d K=%d", N, K);
-  GemvArgs g{};
-  g.w0 = reinterpret_cast<const u32x4_t*>(w0);
-  g.w1 = reinterpret_cast<const u32x4_t*>(w1);
-  g.sz0 = reinterpret_cast<const uint32_t*>(sz0);
-  g.sz1 = reinterpret_cast<const uint32_t*>(sz1);
-  g.x = x;
-  g.ldx = ldx;
-  g.y = y;
-  g.ldy = N;
-  g.alpha = 1.f;
-  g.act = DIHIP_ACT_NONE;
-  g.M = grouped ? 4 : 1;
-  g.slot_rows = group_rows;
-  g.slot_nrows = group_nrows;
-  g.N = N;
-  g.K = K;
-  g.KT = d.KT;
-  g.NTILES = d.NTILES;
-  g.Gp = lowp_dims(4, N, K, group_size).Gp;
-  g.ktpg = gp.ktpg;
-  g.kgroups = gp.kgroups;
-  g.upb = gp.upb;
-  g.nu_q = d.NTILES / gp.blocks;
-  g.nu_r = d.NTILES % gp.blocks;
-  g.WK = gp.WK;
-  g.WN = gp.WN;
-  g.RS = gp.RS;
-  fill_kcut(g);
-  g.slot_expert = slot_expert;
-  g.w_estride = (size_t)d.NTILES * d.KT * 64;       // u32x4 per expert
-  g.sz_estride = (size_t)d.NTILES * g.Gp * 16;      // u32 per expert
-  g.x_div = x_div;
-  g.nslots = nslots;
-  const bool gpt = gp.ktpg == 1;
-  hipError_t e = hipErrorInvalidValue;
-#define SLOT_GO(W_, EPI_, G_)                                                                                          \
-  if (wbits == W_ && epi == EPI_ && (int)gpt == G_)                                                                    \
-    e = grouped ? launch_gemv_slots<W_, DIHIP_BF16, EPI_, G_, 4>(g, gp.blocks, gp.lds_bytes, stream)                   \
-                : launch_gemv_slots<W_, DIHIP_BF16, EPI_, G_, 1>(g, gp.blocks, gp.lds_bytes, stream);
-  SLOT_GO(8, EPI_SWIGLU, 0) SLOT_GO(8, EPI_STD, 0) SLOT_GO(8, EPI_SWIGLU, 1) SLOT_GO(8, EPI_STD, 1)
-  SLOT_GO(4, EPI_SWIGLU, 0) SLOT_GO(4, EPI_STD, 0) SLOT_GO(4, EPI_SWIGLU, 1) SLOT_GO(4, EPI_STD, 1)
-#undef SLOT_GO
-  DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "moe: expert GEMV launch failed: %s", hipGetErrorString(e));
-  return DIHIP_SUCCESS;
-}
-
-static int run_gemm(hipStream_t stream, const GemmCall& c) {
-  DIHIP_REQUIRE(c.M >= 0 && c.N > 0 && c.K > 0, DIHIP_PARAM_ERROR, "gemm_lowp: bad shape M=%d N=%d K=%d",
-                c.M, c.N, c.K);
-  if (c.M == 0) return DIHIP_SUCCESS;  // empty batch
-  DIHIP_REQUIRE(c.dtype == DIHIP_BF16 || c.dtype == DIHIP_F16, DIHIP_PARAM_ERROR,
-                "gemm_lowp: activation type must be FLOAT16 or BFLOAT16 (gemm_a16w8.cpp:21-125)");
-  DIHIP_REQUIRE(c.group_size <= 0 || c.group_size % 32 == 0, DIHIP_PARAM_ERROR,
-                "gemm_lowp: GroupSize %d must be a multiple of 32", c.group_size);
-  DIHIP_REQUIRE(c.x && c.w0 && (c.sz0 || c.wbits == 16), DIHIP_PARAM_ERROR, "gemm_lowp: null input pointer");
-  const bool dual = c.epi == EPI_SWIGLU;
-  const LowpDims d = lowp_dims(c.wbits, c.N, c.K, c.group_size);
-  const bool gemv_aligned = (c.K == d.Kp) && (c.ldx % 8 == 0) && (reinterpret_cast<uintptr_t>(c.x) % 16 == 0) &&
-                            (c.pro == PRO_PLAIN || reinterpret_cast<uintptr_t>(c.gamma) % 16 == 0);
-  const bool f16_std = c.dtype == DIHIP_F16;  // every form of the decode GEMV exists for f16 as well
-  const bool want_frag = c.x_layout == DIHIP_ACT_FRAG32 || c.y_layout == DIHIP_ACT_FRAG32;  // small-batch kernel only
-  DIHIP_REQUIRE(!c.rowsq || (c.M > 4 && c.M <= 32 && c.dtype == DIHIP_BF16 && c.rowsq_parts > 0 && c.epi != EPI_ADDTO), DIHIP_PARAM_ERROR,
-                "gemm_lowp: deferred row norms are taken by the small-batch kernels only (4 < M <= 32, bf16); see dihip_prenorm_rowsq_supported");
-  if (c.n_parts) *c.n_parts = 0;
-  if ((c.dtype == DIHIP_BF16 || f16_std) && gemv_stream_enabled() && gemv_aligned && !want_frag) {
-    const GemvPlan gp = make_gemv_plan(c.wbits, c.M, c.N, c.K, c.group_size, dual);
-    if (gp.ok) {
-      GemvArgs g{};
-      g.w0 = reinterpret_cast<const u32x4_t*>(c.w0);
-      g.w1 = reinterpret_cast<const u32x4_t*>(c.w1);
-      g.sz0 = reinterpret_cast<const uint32_t*>(c.sz0);
-      g.sz1 = reinterpret_cast<const uint32_t*>(c.sz1);
-      g.x = c.x;
-      g.ldx = c.ldx;
-      g.gamma = c.gamma;
-      g.eps = c.eps;
-      g.bias = c.bias;
-      g.residual = c.residual;
-      g.y = c.y;
-      g.ldy = c.N;
-      g.h_res = c.h_res;
-      g.h_out = c.h_out;
-      g.alpha = c.alpha;
-      g.act = c.act;
-      g.M = c.M;
-      g.N = c.N;
-      g.K = c.K;
-      g.KT = d.KT;
-      g.NTILES = d.NTILES;
-      g.Gp = lowp_dims(4, c.N, c.K, c.group_size).Gp;
-      g.ktpg = gp.ktpg;
-      g.kgroups = gp.kgroups;
-      g.upb = gp.upb;
-      g.nu_q = d.NTILES / gp.blocks;
-      g.nu_r = d.NTILES % gp.blocks;
-      g.WK = gp.WK;
-      g.WN = gp.WN;
-      g.RS = gp.RS;
-      fill_kcut(g);
-      g.trace = debug_trace_buffer((size_t)gp.blocks * GEMV_WAVES * 64);
-      hipError_t e = hipErrorInvalidValue;
-      if (f16_std && c.wbits == 4) e = dispatch_gemv<4, DIHIP_F16>(gp, c.pro, c.epi, g, stream);
-      else if (f16_std && c.wbits == 8) e = dispatch_gemv<8, DIHIP_F16>(gp, c.pro, c.epi, g, stream);
-      else if (f16_std && c.wbits == 16) e = dispatch_gemv<16, DIHIP_F16>(gp, c.pro, c.epi, g, stream);
-      else if (c.wbits == 4) e = dispatch_gemv<4, DIHIP_BF16>(gp, c.pro, c.epi, g, stream);
-      else if (c.wbits == 8) e = dispatch_gemv<8, DIHIP_BF16>(gp, c.pro, c.epi, g, stream);
-      else if (c.wbits == 16) e = dispatch_gemv<16, DIHIP_BF16>(gp, c.pro, c.epi, g, stream);
-      DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "gemv_stream: launch failed (wbits=%d MR=%d pro=%d epi=%d): %s",
-                    c.wbits, gp.MR, c.pro, c.epi, hipGetErrorString(e));
-      return DIHIP_SUCCESS;
-    }
-  }
-  // batched decode with FRAG32 activations: panels of 8 column tiles sharing x through LDS (gemm_panel_kernel.hpp)
-  const bool f16_act = c.dtype == DIHIP_F16;  // (round 5: the small-batch and context-phase kernels are instantiated for f16 as well)
-  if ((c.dtype == DIHIP_BF16 || f16_act) && gemv_stream_enabled() && c.x_layout == DIHIP_ACT_FRAG32 && c.pro == PRO_PLAIN && c.M > 4 &&
-      c.M <= 32 && c.wbits != 16 && c.K == d.Kp && (d.group == 0 || d.group % d.KTILE == 0)) {
-    const KslicePlan kp = make_kslice_plan(c.wbits, c.M, c.N, c.K, c.group_size, dual);
-    if (kp.ok) {
-      DIHIP_REQUIRE(kp.nslices == 1 || (c.ws && c.ws_bytes >= kp.slab_bytes), DIHIP_MEMORY_ERROR,
-                    "gemm_kslice: workspace too small for the split-K slab (%zu < %zu)", c.ws_bytes, kp.slab_bytes);
-      PanelArgs g{};
-      g.w0 = reinterpret_cast<const u32x4_t*>(c.w0);
-      g.w1 = reinterpret_cast<const u32x4_t*>(c.w1);
-      g.sz0 = reinterpret_cast<const uint32_t*>(c.sz0);
-      g.sz1 = reinterpret_cast<const uint32_t*>(c.sz1);
-      g.x = c.x;
-      g.bias = c.bias;
-      g.residual = c.residual;
-      g.y = c.y;
-      g.ldy = c.N;
-      g.h_res = c.h_res;
-      g.h_out = c.h_out;
-      g.alpha = c.alpha;
-      g.act = c.act;
-      g.M = c.M;
-      g.N = c.N;
-      g.K = c.K;
-      g.KT = d.KT;
-      g.NTILES = d.NTILES;
-      g.Gp = lowp_dims(4, c.N, c.K, c.group_size).Gp;
-      g.ktpg = d.group ? d.group / d.KTILE : (1 << 28);
-      g.nslices = kp.nslices;
-      g.slab = reinterpret_cast<float*>(c.ws);
-      g.yfrag = c.y_layout == DIHIP_ACT_FRAG32;
-      g.nunits = kp.nunits;
-      g.trace = debug_trace_buffer((size_t)kp.groups * kp.nslices * KSL_WAVES * 64);
-      if (c.epi == EPI_ADDTO && c.n_gamma && c.n_out && g.nslices > 1 && c.N % 4 == 0 && c.N <= 8192) {
-        g.n_gamma = c.n_gamma;
-        g.n_eps = c.n_eps;
-        g.n_out = c.n_out;
-        g.n_frag_mt = c.n_frag_mt;
-        if (c.n_done) *c.n_done = true;
-      }
-      const bool gpt = g.ktpg == 1;
-      const int mt = c.M > 16 ? 2 : 1;
-      const int waves = kp.waves;
-      if (c.rowsq) {  // deferred row norms: in the epilogue (unsplit K) or in the slab reduction
-        g.rowsq = c.rowsq;
-        g.rowsq_parts = c.rowsq_parts;
-        g.rowsq_eps = c.rowsq_eps;
-      }
-      hipError_t e = hipErrorInvalidValue;
-#define KSLICE_GO(W_, MT_, EPI_, G_) \
-      if (c.wbits == W_ && mt == MT_ && c.epi == EPI_ && (int)gpt == G_)                                                       \
-        e = f16_act ? launch_gemm_kslice<W_, DIHIP_F16, MT_, EPI_, G_>(g, kp.groups, waves, stream)                            \
-                    : launch_gemm_kslice<W_, DIHIP_BF16, MT_, EPI_, G_>(g, kp.groups, waves, stream);
-#define KSLICE_ALL(W_, G_) KSLICE_GO(W_, 1, EPI_STD, G_) KSLICE_GO(W_, 2, EPI_STD, G_) KSLICE_GO(W_, 1, EPI_SWIGLU, G_) \
-      KSLICE_GO(W_, 2, EPI_SWIGLU, G_) KSLICE_GO(W_, 1, EPI_ADDTO, G_) KSLICE_GO(W_, 2, EPI_ADDTO, G_)
-      if (c.rowsq && kp.nslices == 1) {  // the deferred-RMSNorm consumer has its own instantiations (bf16)
-#define KSLICE_RS_GO(W_, MT_, EPI_, G_) \
-        if (c.wbits == W_ && mt == MT_ && c.epi == EPI_ && (int)gpt == G_) e = launch_gemm_kslice_rs<W_, MT_, EPI_, G_>(g, kp.groups, waves, stream);
-#define KSLICE_RS_ALL(W_, G_) KSLICE_RS_GO(W_, 1, EPI_STD, G_) KSLICE_RS_GO(W_, 2, EPI_STD, G_) KSLICE_RS_GO(W_, 1, EPI_SWIGLU, G_) KSLICE_RS_GO(W_, 2, EPI_SWIGLU, G_)
-        KSLICE_RS_ALL(4, 0) KSLICE_RS_ALL(4, 1) KSLICE_RS_ALL(8, 0)
-#undef KSLICE_RS_ALL
-#undef KSLICE_RS_GO
-      } else {
-      KSLICE_ALL(4, 0) KSLICE_ALL(4, 1) KSLICE_ALL(8, 0)  // W8 with a group per k-tile (g64) is excluded by the plan: not instantiated
-      }
-#undef KSLICE_ALL
-#undef KSLICE_GO
-      DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "gemm_kslice: launch failed (wbits=%d M=%d epi=%d): %s", c.wbits, c.M,
-                    c.epi, hipGetErrorString(e));
-      return DIHIP_SUCCESS;
-    }
-    const PanelPlan pp = make_panel_plan(c.wbits, c.M, c.N, c.K, c.group_size, dual);
-    if (pp.ok) {
-      DIHIP_REQUIRE(pp.nslices == 1 || (c.ws && c.ws_bytes >= pp.slab_bytes), DIHIP_MEMORY_ERROR,
-                    "gemm_panel: workspace too small for the split-K slab (%zu < %zu)", c.ws_bytes, pp.slab_bytes);
-      PanelArgs g{};
-      g.w0 = reinterpret_cast<const u32x4_t*>(c.w0);
-      g.w1 = reinterpret_cast<const u32x4_t*>(c.w1);
-      g.sz0 = reinterpret_cast<const uint32_t*>(c.sz0);
-      g.sz1 = reinterpret_cast<const uint32_t*>(c.sz1);
-      g.x = c.x;
-      g.bias = c.bias;
-      g.residual = c.residual;
-      g.y = c.y;
-      g.ldy = c.N;
-      g.h_res = c.h_res;
-      g.h_out = c.h_out;
-      g.alpha = c.alpha;
-      g.act = c.act;
-      g.M = c.M;
-      g.N = c.N;
-      g.K = c.K;
-      g.KT = d.KT;
-      g.NTILES = d.NTILES;
-      g.Gp = lowp_dims(4, c.N, c.K, c.group_size).Gp;
-      g.ktpg = d.group ? d.group / d.KTILE : (1 << 28);
-      g.ktps = pp.ktps;
-      g.nslices = pp.nslices;
-      g.slab = reinterpret_cast<float*>(c.ws);
-      g.yfrag = c.y_layout == DIHIP_ACT_FRAG32;
-      if (c.epi == EPI_ADDTO && c.n_gamma && c.n_out && g.nslices > 1 && c.N % 4 == 0 && c.N <= 8192) {
-        g.n_gamma = c.n_gamma;
-        g.n_eps = c.n_eps;
-        g.n_out = c.n_out;
-        g.n_frag_mt = c.n_frag_mt;
-        if (c.n_done) *c.n_done = true;
-      }
-      const bool gpt = g.ktpg == 1;
-      const int mt = c.M > 16 ? 2 : 1;
-      if (c.rowsq) {
-        DIHIP_REQUIRE(pp.nslices > 1, DIHIP_PARAM_ERROR, "gemm_panel: deferred row norms need the split-K reduction; see dihip_prenorm_rowsq_supported");
-        g.rowsq = c.rowsq;
-        g.rowsq_parts = c.rowsq_parts;
-        g.rowsq_eps = c.rowsq_eps;
-      }
-      hipError_t e = hipErrorInvalidValue;
-#define PANEL_GO(W_, MT_, EPI_, G_) \
-      if (c.wbits == W_ && mt == MT_ && c.epi == EPI_ && (int)gpt == G_)                                          \
-        e = f16_act ? launch_gemm_panel<W_, DIHIP_F16, MT_, EPI_, G_>(g, pp.panels, stream)                       \
-                    : launch_gemm_panel<W_, DIHIP_BF16, MT_, EPI_, G_>(g, pp.panels, stream);
-#define PANEL_ALL(W_, G_) PANEL_GO(W_, 1, EPI_STD, G_) PANEL_GO(W_, 2, EPI_STD, G_) PANEL_GO(W_, 1, EPI_SWIGLU, G_) \
-      PANEL_GO(W_, 2, EPI_SWIGLU, G_) PANEL_GO(W_, 1, EPI_ADDTO, G_) PANEL_GO(W_, 2, EPI_ADDTO, G_)
-      PANEL_ALL(4, 0) PANEL_ALL(4, 1) PANEL_ALL(8, 0) PANEL_ALL(8, 1)
-#undef PANEL_ALL
-#undef PANEL_GO
-      DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "gemm_panel: launch failed (wbits=%d M=%d epi=%d): %s", c.wbits, c.M,
-                    c.epi, hipGetErrorString(e));
-      return DIHIP_SUCCESS;
-    }
-  }
-  // small decode batches whose activations do not fit in LDS: register-resident A (gemv_batch_kernel.hpp)
-  if ((c.dtype == DIHIP_BF16 || f16_act) && gemv_stream_enabled() && gemv_aligned && c.pro == PRO_PLAIN && c.M > 1 && c.M <= 32 &&
-      c.wbits != 16 && (d.group == 0 || d.group % d.KTILE == 0)) {
-    GembArgs g{};
-    g.w0 = reinterpret_cast<const u32x4_t*>(c.w0);
-    g.w1 = reinterpret_cast<const u32x4_t*>(c.w1);
-    g.sz0 = reinterpret_cast<const uint32_t*>(c.sz0);
-    g.sz1 = reinterpret_cast<const uint32_t*>(c.sz1);
-    g.x = c.x;
-    g.ldx = c.ldx;
-    g.bias = c.bias;
-    g.residual = c.residual;
-    g.y = c.y;
-    g.ldy = c.N;
-    g.h_res = c.h_res;
-    g.h_out = c.h_out;
-    g.alpha = c.alpha;
-    g.act = c.act;
-    g.M = c.M;
-    g.N = c.N;
-    g.K = c.K;
-    g.KT = d.KT;
-    g.NTILES = d.NTILES;
-    g.Gp = lowp_dims(4, c.N, c.K, c.group_size).Gp;
-    g.ktpg = d.group ? d.group / d.KTILE : (1 << 28);
-    g.kgroups = d.group ? (d.KT + g.ktpg - 1) / g.ktpg : d.KT;
-    const bool gpt = c.wbits != 16 && g.ktpg == 1;
-    const int mt = c.M > 16 ? 2 : 1;
-    g.xfrag = c.x_layout == DIHIP_ACT_FRAG32;
-    g.yfrag = c.y_layout == DIHIP_ACT_FRAG32;
-    // at most one workgroup per CU; a workgroup with several units walks them two at a time so that
-    // one pass over the activations (L2 -> registers) feeds two column tiles
-    static const int env_upb = env_int("DIHIP_GEMB_UPB", 0), env_nt = env_int("DIHIP_GEMB_NT", 0);  // diagnostics
-    int ncu = cached_num_cus();
-    if (ncu <= 0) ncu = 256;
-    g.upb = env_upb > 0 ? env_upb : (d.NTILES <= ncu ? 1 : (d.NTILES + ncu - 1) / ncu);
-    const int nt = env_nt > 0 ? std::min(env_nt, 2) : (g.upb >= 2 ? 2 : 1);
-    const int blocks = (d.NTILES + g.upb - 1) / g.upb;
-    if (c.epi == EPI_ADDTO && c.n_rowsq && c.n_gamma && c.n_out && c.n_parts && c.dtype == DIHIP_BF16 && g.upb <= GEMB_MAXU &&
-        (size_t)blocks * 32 * sizeof(float) <= c.n_rowsq_bytes) {  // deferred RMSNorm, producer side
-      g.n_gamma = c.n_gamma;
-      g.n_out = c.n_out;
-      g.n_frag_mt = c.n_frag_mt;
-      g.n_rowsq = c.n_rowsq;
-      *c.n_parts = blocks;
-      if (c.n_done) *c.n_done = true;
-    }
-    if (c.rowsq) {
-      DIHIP_REQUIRE(c.epi == EPI_STD, DIHIP_PARAM_ERROR, "gemv_batch: deferred row norms on the plain epilogue only; see dihip_prenorm_rowsq_supported");
-      DIHIP_REQUIRE(c.rowsq_parts <= 16 * (GEMB_THREADS / 32), DIHIP_PARAM_ERROR, "gemv_batch: more than %d row-norm parts", 16 * (GEMB_THREADS / 32));
-      g.rowsq = c.rowsq;
-      g.rowsq_parts = c.rowsq_parts;
-      g.rowsq_eps = c.rowsq_eps;
-    }
-    hipError_t e = hipErrorInvalidValue;
-#define GEMB_GO(W_, MT_, NT_, EPI_, G_) \
-    if (c.wbits == W_ && mt == MT_ && nt == NT_ && c.epi == EPI_ && (int)gpt == G_) \
-      e = f16_act ? launch_gemv_batch<W_, DIHIP_F16, MT_, NT_, EPI_, G_>(g, blocks, stream)  \
-                  : launch_gemv_batch<W_, DIHIP_BF16, MT_, NT_, EPI_, G_>(g, blocks, stream);
-#define GEMB_EPIS(W_, MT_, NT_, G_) GEMB_GO(W_, MT_, NT_, EPI_STD, G_) GEMB_GO(W_, MT_, NT_, EPI_SWIGLU, G_) GEMB_GO(W_, MT_, NT_, EPI_ADDTO, G_)
-#define GEMB_ALL(W_, G_) GEMB_EPIS(W_, 1, 1, G_) GEMB_EPIS(W_, 2, 1, G_) GEMB_EPIS(W_, 1, 2, G_) GEMB_EPIS(W_, 2, 2, G_)
-    GEMB_ALL(4, 0) GEMB_ALL(4, 1) GEMB_ALL(8, 0) GEMB_ALL(8, 1)
-#undef GEMB_ALL
-#undef GEMB_EPIS
-#undef GEMB_GO
-    DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "gemv_batch: launch failed (wbits=%d M=%d epi=%d): %s", c.wbits, c.M, c.epi,
-                  hipGetErrorString(e));
-    return DIHIP_SUCCESS;
-  }
-  DIHIP_REQUIRE(!want_frag, DIHIP_PARAM_ERROR,
-                "gemm_lowp: the FRAG32 activation layout needs the small-batch kernel (see dihip_gemm_lowp_prefers_frag)");
-  DIHIP_REQUIRE(!c.rowsq, DIHIP_PARAM_ERROR, "gemm_lowp: this shape is not served by a kernel that takes deferred row norms");
-  // context phase (M >= 64 rows): 128 x 256 workgroup tiles, A through LDS, every weight byte read once per 128 rows
-  // (gemm_prefill_kernel.hpp).  DIHIP_GEMM_PREFILL=0 keeps the general kernel (A/B, diagnostics).
-  static const bool prefill_on = !env_off("DIHIP_GEMM_PREFILL");
-  if (prefill_on && (c.dtype == DIHIP_BF16 || f16_act) && c.pro == PRO_PLAIN && c.M >= 64 && (c.wbits == 4 || c.wbits == 8) && gemv_aligned &&
-      (d.group == 0 || d.group % d.KTILE == 0) && (c.epi != EPI_SWIGLU || (c.w1 && c.sz1))) {
-    PrefillArgs g{};
-    g.w0 = reinterpret_cast<const u32x4_t*>(c.w0);
-    g.w1 = reinterpret_cast<const u32x4_t*>(c.w1);
-    g.sz0 = reinterpret_cast<const uint32_t*>(c.sz0);
-    g.sz1 = reinterpret_cast<const uint32_t*>(c.sz1);
-    g.x = c.x;
-    g.ldx = c.ldx;
-    g.bias = c.bias;
-    g.residual = c.residual;
-    g.y = c.y;
-    g.ldy = c.N;
-    g.h_res = c.h_res;
-    g.h_out = c.h_out;
-    g.alpha = c.alpha;
-    g.act = c.act;
-    g.M = c.M;
-    g.N = c.N;
-    g.KT = d.KT;
-    g.NTILES = d.NTILES;
-    g.Gp = lowp_dims(4, c.N, c.K, c.group_size).Gp;
-    g.ktpg = d.group ? d.group / d.KTILE : (1 << 28);
-    const int tiles_per_block = dual ? PF_WN * PF_CW / 2 : PF_WN * PF_CW;
-    g.col_blocks = (d.NTILES + tiles_per_block - 1) / tiles_per_block;
-    g.tail_cb = g.col_blocks;
-    g.ksplit = 1;
-    int blocks = g.col_blocks * ((c.M + PF_BM - 1) / PF_BM);
-    const PrefillTail pt = prefill_tail_plan(c.wbits, c.M, c.N, c.K, c.group_size, dual);
-    if (pt.ksplit > 1 && c.ws && c.ws_bytes >= pt.slab_bytes && reinterpret_cast<uintptr_t>(c.ws) % 16 == 0) {
-      g.tail_cb = pt.tail_cb;
-      g.ksplit = pt.ksplit;
-      g.slab = reinterpret_cast<float*>(c.ws);
-      blocks = pt.tail_cb * pt.mblocks + (pt.col_blocks - pt.tail_cb) * pt.mblocks * pt.ksplit;
-    }
-    g.trace = debug_trace_buffer((size_t)blocks * PF_WAVES * 4 * 8 * sizeof(unsigned long long));
-    const bool gpt = g.ktpg == 1;
-    hipError_t e = hipErrorInvalidValue;
-#define PREFILL_GO(W_, EPI_, G_) \
-    if (c.wbits == W_ && c.epi == EPI_ && (int)gpt == G_)                                          \
-      e = f16_act ? launch_gemm_prefill<W_, DIHIP_F16, EPI_, G_>(g, blocks, stream) : launch_gemm_prefill<W_, DIHIP_BF16, EPI_, G_>(g, blocks, stream);
-#define PREFILL_ALL(W_) PREFILL_GO(W_, EPI_STD, 0) PREFILL_GO(W_, EPI_STD, 1) PREFILL_GO(W_, EPI_SWIGLU, 0) PREFILL_GO(W_, EPI_SWIGLU, 1) \
-    PREFILL_GO(W_, EPI_ADDTO, 0) PREFILL_GO(W_, EPI_ADDTO, 1)
-    PREFILL_ALL(4) PREFILL_ALL(8)
-#undef PREFILL_ALL
-#undef PREFILL_GO
-    DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "gemm_prefill: launch failed (wbits=%d M=%d epi=%d): %s", c.wbits, c.M, c.epi,
-                  hipGetErrorString(e));
-    return DIHIP_SUCCESS;
-  }
-  const GemmPlan p = make_plan(c.wbits, c.M, c.N, c.K, c.group_size, dual);
-  DIHIP_REQUIRE((size_t)p.col_blocks * p.m_blocks * sizeof(unsigned) <= GEMM_SYNC_BYTES, DIHIP_EXCEED_LIMIT_ERROR,
-                "gemm_lowp: too many tiles for the sync buffer");
-  unsigned* counters = reinterpret_cast<unsigned*>(c.sync);
-  float* slabs = reinterpret_cast<float*>(c.ws);
-  if (p.splitk > 1) {
-    size_t need = p.slab_bytes + (c.sync ? 0 : GEMM_SYNC_BYTES);
-    DIHIP_REQUIRE(c.ws && c.ws_bytes >= need, DIHIP_MEMORY_ERROR,
-                  "gemm_lowp: workspace too small (%zu < %zu)", c.ws_bytes, need);
-    if (!c.sync) {
-      counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(c.ws) + p.slab_bytes);
-      DIHIP_CHECK_HIP(hipMemsetAsync(counters, 0, (size_t)p.col_blocks * p.m_blocks * sizeof(unsigned), stream),
-                      DIHIP_RUNTIME_ERROR);
-    }
-  }
-  GemmArgs a{};
-  a.w0 = reinterpret_cast<const u32x4_t*>(c.w0);
-  a.w1 = reinterpret_cast<const u32x4_t*>(c.w1);
-  a.sz0 = reinterpret_cast<const uint32_t*>(c.sz0);
-  a.sz1 = reinterpret_cast<const uint32_t*>(c.sz1);
-  a.x = c.x;
-  a.ldx = c.ldx;
-  a.gamma = c.gamma;
-  a.eps = c.eps;
-  a.slabs = slabs;
-  a.counters = counters;
-  a.bias = c.bias;
-  a.residual = c.residual;
-  a.y = c.y;
-  a.ldy = c.N;
-  a.h_res = c.h_res;
-  a.h_out = c.h_out;
-  a.alpha = c.alpha;
-  a.act = c.act;
-  a.M = c.M;
-  a.N = c.N;
-  a.K = c.K;
-  a.Np = d.Np;
-  a.KT = d.KT;
-  a.NTILES = d.NTILES;
-  a.ksteps_per_group = d.group ? d.group / 32 : (1 << 30);
-  a.Gp = lowp_dims(4, c.N, c.K, c.group_size).Gp;  // the pack kernel sizes Gp for the W4 padding
-  a.splitk = p.splitk;
-  a.ktiles_per_split = p.ktiles_per_split;
-  a.kslice_tiles = p.kslice_tiles;
-  const dim3 grid(p.col_blocks, p.splitk, p.m_blocks);
-  hipError_t e = hipErrorInvalidValue;
-  if (c.wbits == 4 && c.dtype == DIHIP_BF16) e = dispatch<4, DIHIP_BF16>(p, c.pro, c.epi, a, grid, stream);
-  else if (c.wbits == 4 && c.dtype == DIHIP_F16) e = dispatch<4, DIHIP_F16>(p, c.pro, c.epi, a, grid, stream);
-  else if (c.wbits == 8 && c.dtype == DIHIP_BF16) e = dispatch<8, DIHIP_BF16>(p, c.pro, c.epi, a, grid, stream);
-  else if (c.wbits == 8 && c.dtype == DIHIP_F16) e = dispatch<8, DIHIP_F16>(p, c.pro, c.epi, a, grid, stream);
-  else if (c.wbits == 16 && c.dtype == DIHIP_BF16) e = dispatch_dense<DIHIP_BF16>(p, c.pro, c.epi, a, grid, stream);
-  else if (c.wbits == 16 && c.dtype == DIHIP_F16) e = dispatch_dense<DIHIP_F16>(p, c.pro, c.epi, a, grid, stream);
-  DIHIP_REQUIRE(e == hipSuccess, e == hipErrorInvalidValue ? DIHIP_PARAM_ERROR : DIHIP_RUNTIME_ERROR,
-                "gemm_lowp: launch failed (wbits=%d dtype=%d MT=%d NT=%d pro=%d epi=%d): %s", c.wbits, c.dtype,
-                p.MT, p.NT, c.pro, c.epi, hipGetErrorString(e));
-  return DIHIP_SUCCESS;
-}
-
-// true when a PRO_PLAIN bf16 call of this shape runs on the small-batch kernel (which reads FRAG32 faster)
-static bool batch_kernel_eligible(int wbits, int M, int N, int K, int group_size) {
-  if ((wbits != 4 && wbits != 8) || M <= 1 || M > 32 || N <= 0 || K <= 0) return false;
-  if (!gemv_stream_enabled()) return false;
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  return K == d.Kp && (d.group == 0 || d.group % d.KTILE == 0);
-}
-static bool batch_kernel_shape(int wbits, int M, int N, int K, int group_size, bool dual) {
-  return batch_kernel_eligible(wbits, M, N, K, group_size) && !make_gemv_plan(wbits, M, N, K, group_size, dual).ok;
-}
-
 // f32 hidden rows -> FT normalised rows (used by the fused entry points when M > 4); frag_mt > 0: FRAG32 output.
 // One workgroup per row, the row stays in registers (one 16-byte load per 4 columns, all in flight together):
 // a single round trip instead of two dependent passes over h.  cols % 4 == 0, cols <= 256 * 4 * VPT.
@@ -1084,36 +183,349 @@ __global__ void act_frag_convert_kernel(uint16_t* __restrict__ dst, const uint16
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// launch: kernel arguments and the thunk tables (instantiations: *_inst_*.hip)
+// ------------------------------------------------------------------------------------------
+// operands and shape: what every launch has, the expert slots (run_gemv_slots) included
+template <class Args>
+static void fill_operands(Args& g, const void* x, const void* w0, const void* sz0, const void* w1, const void* sz1, void* y, int M,
+                          int N, const LowpDims& d) {
+  g.w0 = reinterpret_cast<const u32x4_t*>(w0);
+  g.w1 = reinterpret_cast<const u32x4_t*>(w1);
+  g.sz0 = reinterpret_cast<const uint32_t*>(sz0);
+  g.sz1 = reinterpret_cast<const uint32_t*>(sz1);
+  g.x = x;
+  g.y = y;
+  g.ldy = N;
+  g.alpha = 1.f;
+  g.act = DIHIP_ACT_NONE;
+  g.M = M;
+  g.N = N;
+  g.KT = d.KT;
+  g.NTILES = d.NTILES;
+  g.Gp = d.Gp_packed;
+}
+// the fields every family's argument struct has
+template <class Args>
+static void fill_common(Args& g, const GemmCall& c, const LowpDims& d) {
+  fill_operands(g, c.x, c.w0, c.sz0, c.w1, c.sz1, c.y, c.M, c.N, d);
+  g.bias = c.bias;
+  g.residual = c.residual;
+  g.h_res = c.h_res;
+  g.h_out = c.h_out;
+  g.alpha = c.alpha;
+  g.act = c.act;
+}
+// deferred row norms handed in (GembArgs / PanelArgs)
+template <class Args>
+static void fill_rowsq(Args& g, const GemmCall& c) {
+  g.rowsq = c.rowsq;
+  g.rowsq_parts = c.rowsq_parts;
+  g.rowsq_eps = c.rowsq_eps;
+}
+// the K-slice and the panel kernel share their arguments
+static void fill_panel(PanelArgs& g, const GemmCall& c, const LowpDims& d, const GemmRoute& r, int nslices) {
+  fill_common(g, c, d);
+  g.K = c.K;
+  g.ktpg = d.ktpg;
+  g.nslices = nslices;
+  g.slab = reinterpret_cast<float*>(c.ws);
+  g.yfrag = c.y_layout == DIHIP_ACT_FRAG32;
+  if (r.norm_in_reduce) {
+    g.n_gamma = c.n_gamma;
+    g.n_eps = c.n_eps;
+    g.n_out = c.n_out;
+    g.n_frag_mt = c.n_frag_mt;
+  }
+  if (c.rowsq) fill_rowsq(g, c);  // applied in the epilogue (unsplit K) or in the slab reduction
+}
+
+#define DIHIP_BOTH_FT(CASES) CASES(DIHIP_BF16) CASES(DIHIP_F16)
+
+static hipError_t launch_route_gemv(const GemmCall& c, const GemmRoute& r, const GemvArgs& g, hipStream_t s) {
+#define GO(W_, FT_, MR_, PRO_, EPI_, G_)                                                                     \
+  if (c.wbits == W_ && c.dtype == FT_ && r.mt == MR_ && r.pro == PRO_ && r.epi == EPI_ && r.gpt == G_) \
+    return launch_gemv_stream<W_, FT_, MR_, PRO_, EPI_, G_>(g, r.grid[0], r.lds_bytes, s);
+#define FORMS(W_, FT_, G_) \
+  GO(W_, FT_, 1, PRO_PLAIN, EPI_STD, G_) \
+  GO(W_, FT_, 4, PRO_PLAIN, EPI_STD, G_) \
+  GO(W_, FT_, 1, PRO_RMSNORM, EPI_STD, G_) \
+  GO(W_, FT_, 4, PRO_RMSNORM, EPI_STD, G_) \
+  GO(W_, FT_, 1, PRO_RMSNORM, EPI_SWIGLU, G_) \
+  GO(W_, FT_, 4, PRO_RMSNORM, EPI_SWIGLU, G_) \
+  GO(W_, FT_, 1, PRO_PLAIN, EPI_SWIGLU, G_) \
+  GO(W_, FT_, 4, PRO_PLAIN, EPI_SWIGLU, G_) \
+  GO(W_, FT_, 1, PRO_PLAIN, EPI_ADDTO, G_) \
+  GO(W_, FT_, 4, PRO_PLAIN, EPI_ADDTO, G_) \
+  GO(W_, FT_, 1, PRO_RMSNORM, EPI_ADDTO, G_) \
+  GO(W_, FT_, 4, PRO_RMSNORM, EPI_ADDTO, G_)
+#define CASES(FT_) FORMS(4, FT_, 0) FORMS(4, FT_, 1) FORMS(8, FT_, 0) FORMS(8, FT_, 1) FORMS(16, FT_, 0)
+  DIHIP_BOTH_FT(CASES)
+#undef CASES
+#undef FORMS
+#undef GO
+  return hipErrorInvalidValue;
+}
+
+static hipError_t launch_route_kslice(const GemmCall& c, const GemmRoute& r, const PanelArgs& g, hipStream_t s) {
+  const int groups = r.kslice.groups, waves = r.kslice.waves;
+#define GO(W_, FT_, MT_, EPI_, G_)                                                                   \
+  if (c.wbits == W_ && c.dtype == FT_ && r.mt == MT_ && r.epi == EPI_ && r.gpt == G_ && !r.rs) \
+    return launch_gemm_kslice<W_, FT_, MT_, EPI_, G_>(g, groups, waves, s);
+#define GO_RS(W_, MT_, EPI_, G_) /* the deferred-RMSNorm consumer has its own instantiations (bf16) */ \
+  if (c.wbits == W_ && r.mt == MT_ && r.epi == EPI_ && r.gpt == G_ && r.rs) return launch_gemm_kslice_rs<W_, MT_, EPI_, G_>(g, groups, waves, s);
+#define FORMS(W_, FT_, G_)                                                                                      \
+  GO(W_, FT_, 1, EPI_STD, G_) GO(W_, FT_, 2, EPI_STD, G_) GO(W_, FT_, 1, EPI_SWIGLU, G_) GO(W_, FT_, 2, EPI_SWIGLU, G_) \
+  GO(W_, FT_, 1, EPI_ADDTO, G_) GO(W_, FT_, 2, EPI_ADDTO, G_)
+#define FORMS_RS(W_, G_) GO_RS(W_, 1, EPI_STD, G_) GO_RS(W_, 2, EPI_STD, G_) GO_RS(W_, 1, EPI_SWIGLU, G_) GO_RS(W_, 2, EPI_SWIGLU, G_)
+#define CASES(FT_) FORMS(4, FT_, 0) FORMS(4, FT_, 1) FORMS(8, FT_, 0)  // W8 with a group per k-tile (g64) is excluded by the plan
+  DIHIP_BOTH_FT(CASES)
+  FORMS_RS(4, 0) FORMS_RS(4, 1) FORMS_RS(8, 0)
+#undef CASES
+#undef FORMS_RS
+#undef FORMS
+#undef GO_RS
+#undef GO
+  return hipErrorInvalidValue;
+}
+
+static hipError_t launch_route_panel(const GemmCall& c, const GemmRoute& r, const PanelArgs& g, hipStream_t s) {
+#define GO(W_, FT_, MT_, EPI_, G_)                                                         \
+  if (c.wbits == W_ && c.dtype == FT_ && r.mt == MT_ && r.epi == EPI_ && r.gpt == G_) \
+    return launch_gemm_panel<W_, FT_, MT_, EPI_, G_>(g, r.panel.panels, s);
+#define FORMS(W_, FT_, G_)                                                                                      \
+  GO(W_, FT_, 1, EPI_STD, G_) GO(W_, FT_, 2, EPI_STD, G_) GO(W_, FT_, 1, EPI_SWIGLU, G_) GO(W_, FT_, 2, EPI_SWIGLU, G_) \
+  GO(W_, FT_, 1, EPI_ADDTO, G_) GO(W_, FT_, 2, EPI_ADDTO, G_)
+#define CASES(FT_) FORMS(4, FT_, 0) FORMS(4, FT_, 1) FORMS(8, FT_, 0) FORMS(8, FT_, 1)
+  DIHIP_BOTH_FT(CASES)
+#undef CASES
+#undef FORMS
+#undef GO
+  return hipErrorInvalidValue;
+}
+
+static hipError_t launch_route_gemb(const GemmCall& c, const GemmRoute& r, const GembArgs& g, hipStream_t s) {
+#define GO(W_, FT_, MT_, NT_, EPI_, G_)                                                                    \
+  if (c.wbits == W_ && c.dtype == FT_ && r.mt == MT_ && r.nt == NT_ && r.epi == EPI_ && r.gpt == G_) \
+    return launch_gemv_batch<W_, FT_, MT_, NT_, EPI_, G_>(g, r.gemb.blocks, s);
+#define EPIS(W_, FT_, MT_, NT_, G_) GO(W_, FT_, MT_, NT_, EPI_STD, G_) GO(W_, FT_, MT_, NT_, EPI_SWIGLU, G_) GO(W_, FT_, MT_, NT_, EPI_ADDTO, G_)
+#define FORMS(W_, FT_, G_) EPIS(W_, FT_, 1, 1, G_) EPIS(W_, FT_, 2, 1, G_) EPIS(W_, FT_, 1, 2, G_) EPIS(W_, FT_, 2, 2, G_)
+#define CASES(FT_) FORMS(4, FT_, 0) FORMS(4, FT_, 1) FORMS(8, FT_, 0) FORMS(8, FT_, 1)
+  DIHIP_BOTH_FT(CASES)
+#undef CASES
+#undef FORMS
+#undef EPIS
+#undef GO
+  return hipErrorInvalidValue;
+}
+
+static hipError_t launch_route_prefill(const GemmCall& c, const GemmRoute& r, const PrefillArgs& g, hipStream_t s) {
+#define GO(W_, FT_, EPI_, G_) \
+  if (c.wbits == W_ && c.dtype == FT_ && r.epi == EPI_ && r.gpt == G_) return launch_gemm_prefill<W_, FT_, EPI_, G_>(g, r.grid[0], s);
+#define FORMS(W_, FT_) GO(W_, FT_, EPI_STD, 0) GO(W_, FT_, EPI_STD, 1) GO(W_, FT_, EPI_SWIGLU, 0) GO(W_, FT_, EPI_SWIGLU, 1) \
+  GO(W_, FT_, EPI_ADDTO, 0) GO(W_, FT_, EPI_ADDTO, 1)
+#define CASES(FT_) FORMS(4, FT_) FORMS(8, FT_)
+  DIHIP_BOTH_FT(CASES)
+#undef CASES
+#undef FORMS
+#undef GO
+  return hipErrorInvalidValue;
+}
+
+static hipError_t launch_route_gemm(const GemmCall& c, const GemmRoute& r, const GemmArgs& a, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]);
+#define GO(W_, FT_, MT_, NT_, PRO_, EPI_)                                                                   \
+  if (c.wbits == W_ && c.dtype == FT_ && r.mt == MT_ && r.nt == NT_ && r.pro == PRO_ && r.epi == EPI_) \
+    return launch_gemm_lowp<W_, FT_, MT_, NT_, PRO_, EPI_>(a, grid, r.lds_bytes, s);
+#define FORMS(W_, FT_) \
+  GO(W_, FT_, 1, 2, PRO_PLAIN, EPI_STD) \
+  GO(W_, FT_, 1, 4, PRO_PLAIN, EPI_STD) \
+  GO(W_, FT_, 2, 2, PRO_PLAIN, EPI_STD) \
+  GO(W_, FT_, 2, 4, PRO_PLAIN, EPI_STD) /* fused decode-step forms: */ \
+  GO(W_, FT_, 1, 2, PRO_RMSNORM, EPI_STD) \
+  GO(W_, FT_, 1, 4, PRO_RMSNORM, EPI_STD) \
+  GO(W_, FT_, 1, 4, PRO_RMSNORM, EPI_SWIGLU) \
+  GO(W_, FT_, 1, 4, PRO_PLAIN, EPI_SWIGLU) \
+  GO(W_, FT_, 2, 4, PRO_PLAIN, EPI_SWIGLU) \
+  GO(W_, FT_, 1, 2, PRO_PLAIN, EPI_ADDTO) \
+  GO(W_, FT_, 1, 4, PRO_PLAIN, EPI_ADDTO) \
+  GO(W_, FT_, 2, 2, PRO_PLAIN, EPI_ADDTO) \
+  GO(W_, FT_, 2, 4, PRO_PLAIN, EPI_ADDTO)
+#define FORMS_DENSE(FT_) /* unquantised weights: lm_head (rmsnorm prologue for M <= 4, f32 logits out) and dense Gemm */ \
+  GO(16, FT_, 1, 4, PRO_RMSNORM, EPI_ADDTO) \
+  GO(16, FT_, 1, 4, PRO_PLAIN, EPI_ADDTO) \
+  GO(16, FT_, 2, 4, PRO_PLAIN, EPI_ADDTO) \
+  GO(16, FT_, 1, 4, PRO_PLAIN, EPI_STD) \
+  GO(16, FT_, 2, 4, PRO_PLAIN, EPI_STD)
+#define CASES(FT_) FORMS(4, FT_) FORMS(8, FT_) FORMS_DENSE(FT_)
+  DIHIP_BOTH_FT(CASES)
+#undef CASES
+#undef FORMS_DENSE
+#undef FORMS
+#undef GO
+  return hipErrorInvalidValue;
+}
+#undef DIHIP_BOTH_FT
+
+static const char* const FAMILY_NAME[] = {"none", "gemv_stream", "gemm_kslice", "gemm_panel", "gemv_batch", "gemm_prefill", "gemm_lowp"};
+
+// validate, plan, fill the family's arguments, launch
+static int run_gemm(hipStream_t stream, const GemmCall& c) {
+  DIHIP_REQUIRE(c.M >= 0 && c.N > 0 && c.K > 0, DIHIP_PARAM_ERROR, "gemm_lowp: bad shape M=%d N=%d K=%d",
+                c.M, c.N, c.K);
+  if (c.M == 0) return DIHIP_SUCCESS;  // empty batch
+  DIHIP_REQUIRE(c.dtype == DIHIP_BF16 || c.dtype == DIHIP_F16, DIHIP_PARAM_ERROR,
+                "gemm_lowp: activation type must be FLOAT16 or BFLOAT16 (gemm_a16w8.cpp:21-125)");
+  DIHIP_REQUIRE(c.group_size <= 0 || c.group_size % 32 == 0, DIHIP_PARAM_ERROR,
+                "gemm_lowp: GroupSize %d must be a multiple of 32", c.group_size);
+  DIHIP_REQUIRE(c.x && c.w0 && (c.sz0 || c.wbits == 16), DIHIP_PARAM_ERROR, "gemm_lowp: null input pointer");
+  if (c.n_parts) *c.n_parts = 0;
+
+  const GemmRoute r = plan_gemm(describe(c));
+  if (r.family == FAM_NONE) {
+    if (r.status == DIHIP_MEMORY_ERROR) set_last_error("%s (%zu < %zu)", r.error, c.ws ? c.ws_bytes : (size_t)0, r.need_bytes);
+    else set_last_error("%s", r.error);
+    return r.status;
+  }
+  if (c.n_done && (r.norm_in_reduce || r.prenorm_parts > 0)) *c.n_done = true;
+  if (r.prenorm_parts > 0) *c.n_parts = r.prenorm_parts;
+
+  const LowpDims d = lowp_dims(c.wbits, c.N, c.K, c.group_size);
+  hipError_t e = hipErrorInvalidValue;
+  switch (r.family) {
+    case FAM_GEMV_STREAM: {
+      GemvArgs g{};
+      fill_common(g, c, d);
+      g.ldx = c.ldx;
+      g.gamma = c.gamma;
+      g.eps = c.eps;
+      g.K = c.K;
+      fill_gemv_plan(&g, r.gemv, d, r.gemv.blocks);
+      g.trace = debug_trace_buffer((size_t)r.gemv.blocks * GEMV_WAVES * 64);
+      e = launch_route_gemv(c, r, g, stream);
+      break;
+    }
+    case FAM_GEMM_KSLICE: {
+      PanelArgs g{};
+      fill_panel(g, c, d, r, r.kslice.nslices);
+      g.nunits = r.kslice.nunits;
+      g.trace = debug_trace_buffer((size_t)r.kslice.groups * r.kslice.nslices * KSL_WAVES * 64);
+      e = launch_route_kslice(c, r, g, stream);
+      break;
+    }
+    case FAM_GEMM_PANEL: {
+      PanelArgs g{};
+      fill_panel(g, c, d, r, r.panel.nslices);
+      g.ktps = r.panel.ktps;
+      e = launch_route_panel(c, r, g, stream);
+      break;
+    }
+    case FAM_GEMV_BATCH: {
+      DIHIP_REQUIRE(!c.rowsq || c.rowsq_parts <= 16 * (GEMB_THREADS / 32), DIHIP_PARAM_ERROR, "gemv_batch: more than %d row-norm parts",
+                    16 * (GEMB_THREADS / 32));
+      GembArgs g{};
+      fill_common(g, c, d);
+      g.ldx = c.ldx;
+      g.K = c.K;
+      g.ktpg = d.ktpg;
+      g.kgroups = d.group ? (d.KT + g.ktpg - 1) / g.ktpg : d.KT;
+      g.xfrag = c.x_layout == DIHIP_ACT_FRAG32;
+      g.yfrag = c.y_layout == DIHIP_ACT_FRAG32;
+      g.upb = r.gemb.upb;
+      if (r.prenorm_parts > 0) {  // deferred RMSNorm, producer side
+        g.n_gamma = c.n_gamma;
+        g.n_out = c.n_out;
+        g.n_frag_mt = c.n_frag_mt;
+        g.n_rowsq = c.n_rowsq;
+      }
+      if (c.rowsq) fill_rowsq(g, c);
+      e = launch_route_gemb(c, r, g, stream);
+      break;
+    }
+    case FAM_GEMM_PREFILL: {
+      PrefillArgs g{};
+      fill_common(g, c, d);
+      g.ldx = c.ldx;
+      g.ktpg = d.ktpg;
+      g.col_blocks = r.prefill.col_blocks;
+      g.tail_cb = r.prefill.tail_cb;
+      g.ksplit = r.prefill.ksplit;
+      if (r.prefill.ksplit > 1) g.slab = reinterpret_cast<float*>(c.ws);
+      g.trace = debug_trace_buffer((size_t)r.grid[0] * PF_WAVES * 4 * 8 * sizeof(unsigned long long));
+      e = launch_route_prefill(c, r, g, stream);
+      break;
+    }
+    default: {
+      GemmArgs a{};
+      fill_common(a, c, d);
+      a.ldx = c.ldx;
+      a.gamma = c.gamma;
+      a.eps = c.eps;
+      a.K = c.K;
+      a.Np = d.Np;
+      a.ksteps_per_group = d.group ? d.group / 32 : (1 << 30);
+      a.splitk = r.gemm.splitk;
+      a.ktiles_per_split = r.gemm.ktiles_per_split;
+      a.kslice_tiles = r.gemm.kslice_tiles;
+      a.slabs = reinterpret_cast<float*>(c.ws);
+      a.counters = reinterpret_cast<unsigned*>(c.sync);
+      if (r.gemm.splitk > 1 && !c.sync) {  // self-contained: the counters follow the slab and are cleared per call
+        a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(c.ws) + r.slab_bytes);
+        DIHIP_CHECK_HIP(hipMemsetAsync(a.counters, 0, (size_t)r.grid[0] * r.grid[2] * sizeof(unsigned), stream), DIHIP_RUNTIME_ERROR);
+      }
+      e = launch_route_gemm(c, r, a, stream);
+    }
+  }
+  DIHIP_REQUIRE(e == hipSuccess, e == hipErrorInvalidValue ? DIHIP_PARAM_ERROR : DIHIP_RUNTIME_ERROR,
+                "%s: launch failed (wbits=%d dtype=%d M=%d mt=%d nt=%d pro=%d epi=%d gpt=%d): %s", FAMILY_NAME[r.family], c.wbits,
+                c.dtype, c.M, r.mt, r.nt, r.pro, r.epi, r.gpt, hipGetErrorString(e));
+  return DIHIP_SUCCESS;
+}
+
+int run_gemv_slots(hipStream_t stream, int wbits, int epi, const void* x, int ldx, int x_div, const void* w0, const void* sz0,
+                   const void* w1, const void* sz1, void* y, int N, int K, int group_size, const int* slot_expert, int nslots,
+                   const int* group_rows, const int* group_nrows) {
+  const bool grouped = group_rows != nullptr;  // slot_expert / nslots then enumerate groups of <= 4 slots (moe.hip)
+  const bool dual = epi == EPI_SWIGLU;
+  const LowpDims d = lowp_dims(wbits, N, K, group_size);
+  DIHIP_REQUIRE(K == d.Kp && (d.group == 0 || d.group % d.KTILE == 0), DIHIP_PARAM_ERROR,
+                "moe: K = %d must be a multiple of the k-tile (%d) and groups whole k-tiles", K, d.KTILE);
+  // slots multiply the grid: about one workgroup per CU over the whole launch, at most 8 units per workgroup
+  int ncu = cached_num_cus();
+  if (ncu <= 0) ncu = 256;
+  const int want = std::max((d.NTILES + 7) / 8, (ncu + nslots - 1) / nslots);
+  const GemvPlan gp = make_gemv_plan(wbits, grouped ? 4 : 1, N, K, group_size, dual, want);
+  DIHIP_REQUIRE(gp.ok && gp.lds_bytes <= 64 * 1024, DIHIP_PARAM_ERROR, "moe: unsupported expert shape N=%d K=%d", N, K);
+  GemvArgs g{};
+  fill_operands(g, x, w0, sz0, w1, sz1, y, grouped ? 4 : 1, N, d);
+  g.ldx = ldx;
+  g.K = K;
+  fill_gemv_plan(&g, gp, d, gp.blocks);
+  g.slot_rows = group_rows;
+  g.slot_nrows = group_nrows;
+  g.slot_expert = slot_expert;
+  g.w_estride = (size_t)d.NTILES * d.KT * 64;       // u32x4 per expert
+  g.sz_estride = (size_t)d.NTILES * g.Gp * 16;      // u32 per expert
+  g.x_div = x_div;
+  g.nslots = nslots;
+  const bool gpt = gp.ktpg == 1;
+  hipError_t e = hipErrorInvalidValue;
+#define SLOT_GO(W_, EPI_, G_)                                                                                          \
+  if (wbits == W_ && epi == EPI_ && (int)gpt == G_)                                                                    \
+    e = grouped ? launch_gemv_slots<W_, DIHIP_BF16, EPI_, G_, 4>(g, gp.blocks, gp.lds_bytes, stream)                   \
+                : launch_gemv_slots<W_, DIHIP_BF16, EPI_, G_, 1>(g, gp.blocks, gp.lds_bytes, stream);
+  SLOT_GO(8, EPI_SWIGLU, 0) SLOT_GO(8, EPI_STD, 0) SLOT_GO(8, EPI_SWIGLU, 1) SLOT_GO(8, EPI_STD, 1)
+  SLOT_GO(4, EPI_SWIGLU, 0) SLOT_GO(4, EPI_STD, 0) SLOT_GO(4, EPI_SWIGLU, 1) SLOT_GO(4, EPI_STD, 1)
+#undef SLOT_GO
+  DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "moe: expert GEMV launch failed: %s", hipGetErrorString(e));
+  return DIHIP_SUCCESS;
+}
+
 }  // namespace dihip
 
 using namespace dihip;
 
 extern "C" {
-
-int dihip_debug_gemv_plan(int wbits, int M, int N, int K, int group_size, int dual, int* blocks, int* upb, int* wk, int* wn,
-                          size_t* lds_bytes) {
-  const GemvPlan p = make_gemv_plan(wbits, M, N, K, group_size, dual != 0);
-  if (!p.ok) return DIHIP_PARAM_ERROR;
-  if (blocks) *blocks = p.blocks;
-  if (upb) *upb = p.upb;
-  if (wk) *wk = p.WK;
-  if (wn) *wn = p.WN;
-  if (lds_bytes) *lds_bytes = p.lds_bytes;
-  return DIHIP_SUCCESS;
-}
-
-size_t dihip_gemm_lowp_packed_weight_bytes(int wbits, int N, int K) {
-  if ((wbits != 4 && wbits != 8) || N <= 0 || K <= 0) return 0;
-  const LowpDims d = lowp_dims(wbits, N, K, -1);
-  return (size_t)d.NTILES * d.KT * 64 * 16;
-}
-
-size_t dihip_gemm_lowp_packed_sz_bytes(int N, int K, int group_size) {
-  if (N <= 0 || K <= 0) return 0;
-  // Kp depends on wbits only through the tile (128 vs 64): size for the larger padding
-  const LowpDims d = lowp_dims(4, N, K, group_size);
-  return (size_t)d.Gp * d.Np * 4;
-}
 
 int dihip_gemm_lowp_pack(void* stream, int wbits, const void* wq, const void* scales, const void* zeros, int N,
                          int K, int group_size, int dtype, void* w_packed, void* sz_packed) {
@@ -1125,7 +537,6 @@ int dihip_gemm_lowp_pack(void* stream, int wbits, const void* wq, const void* sc
                 "gemm_lowp_pack: GroupSize %d must be a multiple of 32", group_size);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  const LowpDims d4 = lowp_dims(4, N, K, group_size);
   const size_t total = (size_t)d.NTILES * d.KT * 64 * 4;
   const int blocks = (int)std::min<size_t>((total + 255) / 256, 65535);
   if (wbits == 4)
@@ -1134,61 +545,57 @@ int dihip_gemm_lowp_pack(void* stream, int wbits, const void* wq, const void* sc
   else
     hipLaunchKernelGGL(pack_w8_kernel, dim3(blocks), dim3(256), 0, s, (const int8_t*)wq, (uint32_t*)w_packed, N, K,
                        d.KT, d.NTILES);
-  const size_t sztotal = (size_t)d4.Gp * d.Np;
+  const size_t sztotal = (size_t)d.Gp_packed * d.Np;
   hipLaunchKernelGGL(pack_sz_kernel, dim3((int)std::min<size_t>((sztotal + 255) / 256, 65535)), dim3(256), 0, s,
-                     (const uint16_t*)scales, (const uint16_t*)zeros, (uint32_t*)sz_packed, N, d.Np, d.G, d4.Gp);
+                     (const uint16_t*)scales, (const uint16_t*)zeros, (uint32_t*)sz_packed, N, d.Np, d.G, d.Gp_packed);
   return launch_status();
 }
 
-size_t dihip_gemm_lowp_sync_bytes(void) { return GEMM_SYNC_BYTES; }
-
-// K parts per tail tile the context-phase GEMM of this shape is launched with on this GPU (1: no tail split; diagnostics / tests)
-int dihip_gemm_prefill_tail_parts(int wbits, int M, int N, int K, int group_size, int dual) {
-  if (M < 64 || N <= 0 || K <= 0) return 1;
-  return prefill_tail_plan(wbits, M, N, K, group_size, dual != 0).ksplit;
+int dihip_dense_pack(void* stream, const void* w_kn, int N, int K, int dtype, void* w_packed) {
+  DIHIP_REQUIRE(N > 0 && K > 0 && w_kn && w_packed, DIHIP_PARAM_ERROR, "dense_pack: bad argument");
+  DIHIP_REQUIRE(dtype == DIHIP_BF16 || dtype == DIHIP_F16, DIHIP_PARAM_ERROR, "dense_pack: dtype");
+  const LowpDims d = lowp_dims(16, N, K, -1);
+  const size_t total = (size_t)d.NTILES * d.KT * 64 * 4;
+  hipLaunchKernelGGL(pack_w16_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), (const uint16_t*)w_kn, (uint32_t*)w_packed, N, K, d.KT,
+                     d.NTILES);
+  return launch_status();
 }
 
-size_t dihip_gemm_lowp_workspace_bytes(int wbits, int M, int N, int K, int group_size) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  // sized for the dual (SwiGLU) form, the self-contained counter area and the M > 4 norm buffer
-  const GemmPlan p1 = make_plan(wbits, M, N, K, group_size, false);
-  const GemmPlan p2 = make_plan(wbits, M, N, K, group_size, true);
-  size_t slab = std::max(p1.slab_bytes, p2.slab_bytes);
-  if (wbits != 16 && M >= 64)
-    slab = std::max(slab, std::max(prefill_tail_plan(wbits, M, N, K, group_size, false).slab_bytes, prefill_tail_plan(wbits, M, N, K, group_size, true).slab_bytes));
-  if (wbits != 16 && M > 4 && M <= 32) {
-    slab = std::max(slab, make_panel_plan(wbits, M, N, K, group_size, false).slab_bytes);
-    slab = std::max(slab, make_panel_plan(wbits, M, N, K, group_size, true).slab_bytes);
-    slab = std::max(slab, make_kslice_plan(wbits, M, N, K, group_size, true, true).slab_bytes);
-  }
-  return slab + GEMM_SYNC_BYTES + (size_t)((M + 15) / 16 * 16) * K * 2 + 512;  // norm rows may be FRAG32
-}
-
-static int gemm_std(void* stream, int wbits, const void* x, const void* w, const void* sz, const void* bias,
-                    const void* residual, void* y, int M, int N, int K, int group_size, int act, float alpha,
-                    void* ws, size_t ws_bytes, void* sync, int dtype) {
+// What every entry point sets: activations x [M, K] with row stride K, one packed weight, alpha = 1.  The rest of the
+// GemmCall (bias, residual, second weight, layouts, norm outputs ...) is the entry point's own.
+static GemmCall make_call(int wbits, int dtype, int pro, int epi, const void* x, const void* w_packed, const void* sz_packed,
+                          void* y, int M, int N, int K, int group_size, void* ws, size_t ws_bytes, void* sync) {
   GemmCall c{};
   c.wbits = wbits;
   c.dtype = dtype;
-  c.pro = PRO_PLAIN;
-  c.epi = EPI_STD;
+  c.pro = pro;
+  c.epi = epi;
   c.x = x;
   c.ldx = K;
-  c.w0 = w;
-  c.sz0 = sz;
-  c.bias = bias;
-  c.residual = residual;
+  c.w0 = w_packed;
+  c.sz0 = sz_packed;
   c.y = y;
   c.M = M;
   c.N = N;
   c.K = K;
   c.group_size = group_size;
-  c.act = act;
-  c.alpha = alpha;
+  c.alpha = 1.f;
   c.ws = ws;
   c.ws_bytes = ws_bytes;
   c.sync = sync;
+  return c;
+}
+
+static int gemm_std(void* stream, int wbits, const void* x, const void* w, const void* sz, const void* bias,
+                    const void* residual, void* y, int M, int N, int K, int group_size, int act, float alpha,
+                    void* ws, size_t ws_bytes, void* sync, int dtype) {
   DIHIP_REQUIRE(y != nullptr || M == 0, DIHIP_PARAM_ERROR, "gemm_lowp: null output");
+  GemmCall c = make_call(wbits, dtype, PRO_PLAIN, EPI_STD, x, w, sz, y, M, N, K, group_size, ws, ws_bytes, sync);
+  c.bias = bias;
+  c.residual = residual;
+  c.act = act;
+  c.alpha = alpha;
   return run_gemm(reinterpret_cast<hipStream_t>(stream), c);
 }
 
@@ -1204,6 +611,18 @@ int dihip_gemm_a16w4(void* stream, const void* x, const void* w_packed, const vo
                      void* ws, size_t ws_bytes, void* sync, int dtype) {
   return gemm_std(stream, 4, x, w_packed, sz_packed, bias, residual, y, M, N, K, group_size, act, alpha, ws,
                   ws_bytes, sync, dtype);
+}
+
+// unquantised 16-bit weights (lm_head / dense Gemm), same kernel family
+int dihip_gemm_a16w16(void* stream, const void* x, const void* w_packed, const void* bias, const void* residual,
+                      void* y, int M, int N, int K, int act, float alpha, void* ws, size_t ws_bytes, void* sync,
+                      int dtype) {
+  GemmCall c = make_call(16, dtype, PRO_PLAIN, EPI_STD, x, w_packed, nullptr, y, M, N, K, -1, ws, ws_bytes, sync);
+  c.bias = bias;
+  c.residual = residual;
+  c.act = act;
+  c.alpha = alpha;
+  return run_gemm(reinterpret_cast<hipStream_t>(stream), c);
 }
 
 // RMSNorm of M rows of the f32 hidden stream into FT rows (row-major or FRAG32)
@@ -1226,28 +645,29 @@ static int launch_rmsnorm_rows(hipStream_t s, const float* h, const void* gamma,
   return launch_status();
 }
 
-// For M > 4 the norm runs as its own small kernel into the tail of `ws`.
-// The normalised rows are private to the call, so they are written in whatever layout the GEMM kernel that
-// follows reads fastest (*x_layout).
-static int norm_to_ws(hipStream_t s, const float* h, const void* gamma, float eps, int M, int K, int dtype, void* ws,
-                      size_t ws_bytes, int wbits, int N, int group_size, bool dual, void** xnorm, size_t* ws_left,
-                      int* x_layout, bool force_frag = false) {
-  const GemmPlan p = make_plan(wbits, M, N, K, group_size, dual);
-  size_t slab = p.slab_bytes;
-  if (wbits != 16 && M >= 64) slab = std::max(slab, prefill_tail_plan(wbits, M, N, K, group_size, dual).slab_bytes);
-  if (wbits != 16 && M > 4 && M <= 32) {
-    slab = std::max(slab, make_panel_plan(wbits, M, N, K, group_size, dual).slab_bytes);
-    slab = std::max(slab, make_kslice_plan(wbits, M, N, K, group_size, dual, true).slab_bytes);
+// The call's activations are RMSNorm(h; gamma, eps).  Up to GEMV_STREAM_MAX_M rows the norm is the decode GEMV's prologue.
+// Beyond, it runs as its own small kernel into the tail of the call's workspace: the normalised rows are private to the
+// call, so they are written in whatever layout the GEMM kernel that follows reads fastest (FRAG32 also when the output is).
+static int set_norm_input(hipStream_t s, GemmCall& c, const float* h, const void* gamma, float eps) {
+  if (c.M <= GEMV_STREAM_MAX_M) {
+    c.pro = PRO_RMSNORM;
+    c.x = h;
+    c.gamma = gamma;
+    c.eps = eps;
+    return DIHIP_SUCCESS;
   }
+  const bool dual = c.epi == EPI_SWIGLU;
+  const size_t slab = lowp_slab_bytes(c.wbits, c.M, c.N, c.K, c.group_size, dual);
   const size_t off = (slab + 255) & ~(size_t)255;
-  const bool frag = force_frag || batch_kernel_shape(wbits, M, N, K, group_size, dual);  // (bf16 and f16: both instantiated since round 5)
-  const int mt = M > 16 ? 2 : 1;
-  const size_t xbytes = frag ? (size_t)mt * 16 * K * 2 : (size_t)M * K * 2;
-  DIHIP_REQUIRE(ws && ws_bytes >= off + xbytes, DIHIP_MEMORY_ERROR, "fused gemm: workspace too small");
-  *xnorm = reinterpret_cast<char*>(ws) + off;
-  *ws_left = off;
-  *x_layout = frag ? DIHIP_ACT_FRAG32 : DIHIP_ACT_ROWMAJOR;
-  return launch_rmsnorm_rows(s, h, gamma, eps, M, K, *xnorm, frag ? mt : 0, dtype);
+  const bool frag = c.y_layout == DIHIP_ACT_FRAG32 || lowp_prefers_frag(c.wbits, c.M, c.N, c.K, c.group_size, dual);
+  const int mt = c.M > 16 ? 2 : 1;
+  const size_t xbytes = frag ? (size_t)mt * 16 * c.K * 2 : (size_t)c.M * c.K * 2;
+  DIHIP_REQUIRE(c.ws && c.ws_bytes >= off + xbytes, DIHIP_MEMORY_ERROR, "fused gemm: workspace too small");
+  void* xnorm = reinterpret_cast<char*>(c.ws) + off;
+  c.x = xnorm;
+  c.ws_bytes = off;
+  c.x_layout = frag ? DIHIP_ACT_FRAG32 : DIHIP_ACT_ROWMAJOR;
+  return launch_rmsnorm_rows(s, h, gamma, eps, c.M, c.K, xnorm, frag ? mt : 0, c.dtype);
 }
 
 int dihip_fused_norm_gemm(void* stream, int wbits, const float* h, const void* gamma, float eps, const void* w_packed,
@@ -1257,39 +677,10 @@ int dihip_fused_norm_gemm(void* stream, int wbits, const float* h, const void* g
   DIHIP_REQUIRE(sync != nullptr, DIHIP_PARAM_ERROR, "fused path needs a sync buffer");
   if (M == 0) return DIHIP_SUCCESS;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GemmCall c{};
-  c.wbits = wbits;
-  c.dtype = dtype;
-  c.epi = EPI_STD;
-  c.w0 = w_packed;
-  c.sz0 = sz_packed;
+  GemmCall c = make_call(wbits, dtype, PRO_PLAIN, EPI_STD, nullptr, w_packed, sz_packed, y, M, N, K, group_size, ws, ws_bytes, sync);
   c.bias = bias;
-  c.y = y;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = group_size;
   c.act = act;
-  c.alpha = 1.f;
-  c.sync = sync;
-  c.ldx = K;
-  if (M <= 4) {
-    c.pro = PRO_RMSNORM;
-    c.x = h;
-    c.gamma = gamma;
-    c.eps = eps;
-    c.ws = ws;
-    c.ws_bytes = ws_bytes;
-  } else {
-    void* xn;
-    size_t left;
-    int st = norm_to_ws(s, h, gamma, eps, M, K, dtype, ws, ws_bytes, wbits, N, group_size, false, &xn, &left, &c.x_layout);
-    if (st) return st;
-    c.pro = PRO_PLAIN;
-    c.x = xn;
-    c.ws = ws;
-    c.ws_bytes = left;
-  }
+  if (int st = set_norm_input(s, c, h, gamma, eps)) return st;
   return run_gemm(s, c);
 }
 
@@ -1307,46 +698,29 @@ int dihip_fused_norm_swiglu_ex(void* stream, int wbits, const float* h, const vo
                                size_t ws_bytes, void* sync, int dtype, int y_layout) {
   DIHIP_REQUIRE(dtype == DIHIP_BF16 || dtype == DIHIP_F16, DIHIP_PARAM_ERROR, "fused path: bf16 or f16 activations");
   DIHIP_REQUIRE(y_layout == DIHIP_ACT_ROWMAJOR || y_layout == DIHIP_ACT_FRAG32, DIHIP_PARAM_ERROR, "fused swiglu: bad y_layout");
-  DIHIP_REQUIRE(y_layout == DIHIP_ACT_ROWMAJOR || (M > 4 && batch_kernel_eligible(wbits, M, N, K, group_size)), DIHIP_PARAM_ERROR,
-                "fused swiglu: FRAG32 output needs the small-batch kernel (4 < M <= 32, K a multiple of the k-tile)");
+  DIHIP_REQUIRE(y_layout == DIHIP_ACT_ROWMAJOR || (M > GEMV_STREAM_MAX_M && lowp_frag_served(wbits, dtype, M, N, K, group_size, true)),
+                DIHIP_PARAM_ERROR, "fused swiglu: FRAG32 output needs the small-batch kernel (4 < M <= 32, K a multiple of the k-tile)");
   DIHIP_REQUIRE(sync != nullptr, DIHIP_PARAM_ERROR, "fused path needs a sync buffer");
   if (M == 0) return DIHIP_SUCCESS;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GemmCall c{};
-  c.wbits = wbits;
-  c.dtype = dtype;
-  c.epi = EPI_SWIGLU;
-  c.w0 = wg_packed;
-  c.sz0 = szg_packed;
+  GemmCall c = make_call(wbits, dtype, PRO_PLAIN, EPI_SWIGLU, nullptr, wg_packed, szg_packed, y, M, N, K, group_size, ws, ws_bytes, sync);
   c.w1 = wu_packed;
   c.sz1 = szu_packed;
-  c.y = y;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = group_size;
-  c.alpha = 1.f;
-  c.sync = sync;
-  c.ldx = K;
   c.y_layout = y_layout;
-  if (M <= 4) {
-    c.pro = PRO_RMSNORM;
-    c.x = h;
-    c.gamma = gamma;
-    c.eps = eps;
-    c.ws = ws;
-    c.ws_bytes = ws_bytes;
-  } else {
-    void* xn;
-    size_t left;
-    int st = norm_to_ws(s, h, gamma, eps, M, K, dtype, ws, ws_bytes, wbits, N, group_size, true, &xn, &left, &c.x_layout,
-                        y_layout == DIHIP_ACT_FRAG32);
-    if (st) return st;
-    c.pro = PRO_PLAIN;
-    c.x = xn;
-    c.ws = ws;
-    c.ws_bytes = left;
-  }
+  if (int st = set_norm_input(s, c, h, gamma, eps)) return st;
+  return run_gemm(s, c);
+}
+
+int dihip_lm_head(void* stream, float* logits, const float* h, const void* gamma, float eps, const void* w_packed,
+                  int M, int N, int K, void* ws, size_t ws_bytes, void* sync, int dtype) {
+  DIHIP_REQUIRE(dtype == DIHIP_BF16 || dtype == DIHIP_F16, DIHIP_PARAM_ERROR, "lm_head: dtype");
+  DIHIP_REQUIRE(logits && h && w_packed && sync, DIHIP_PARAM_ERROR, "lm_head: null pointer");
+  if (M == 0) return DIHIP_SUCCESS;
+  DIHIP_REQUIRE(gamma != nullptr, DIHIP_PARAM_ERROR, "lm_head: needs gamma");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  GemmCall c = make_call(16, dtype, PRO_PLAIN, EPI_ADDTO, nullptr, w_packed, nullptr, nullptr, M, N, K, -1, ws, ws_bytes, sync);
+  c.h_out = logits;
+  if (int st = set_norm_input(s, c, h, gamma, eps)) return st;
   return run_gemm(s, c);
 }
 
@@ -1355,10 +729,6 @@ int dihip_fused_gemm_addto(void* stream, int wbits, const void* x, const void* w
                            size_t ws_bytes, void* sync, int dtype) {
   return dihip_fused_gemm_addto_ex(stream, wbits, x, w_packed, sz_packed, h_res, h_out, M, N, K, group_size, ws, ws_bytes,
                                    sync, dtype, DIHIP_ACT_ROWMAJOR);
-}
-
-int dihip_gemm_lowp_prefers_frag(int wbits, int M, int N, int K, int group_size, int dual) {
-  return batch_kernel_shape(wbits, M, N, K, group_size, dual != 0) ? 1 : 0;
 }
 
 size_t dihip_act_frag_bytes(int M, int K) {
@@ -1389,26 +759,10 @@ int dihip_fused_gemm_addto_ex(void* stream, int wbits, const void* x, const void
   DIHIP_REQUIRE(x_layout == DIHIP_ACT_ROWMAJOR || x_layout == DIHIP_ACT_FRAG32, DIHIP_PARAM_ERROR, "fused addto: bad x_layout");
   // h_res may be NULL: then h_out = x . W (row-parallel TP ranks other than 0, gemm_op.cpp:133-137)
   DIHIP_REQUIRE(sync != nullptr && h_out, DIHIP_PARAM_ERROR, "fused addto: null pointer");
-  GemmCall c{};
-  c.wbits = wbits;
-  c.dtype = dtype;
-  c.pro = PRO_PLAIN;
-  c.epi = EPI_ADDTO;
-  c.x = x;
-  c.ldx = K;
+  GemmCall c = make_call(wbits, dtype, PRO_PLAIN, EPI_ADDTO, x, w_packed, sz_packed, nullptr, M, N, K, group_size, ws, ws_bytes, sync);
   c.x_layout = x_layout;
-  c.w0 = w_packed;
-  c.sz0 = sz_packed;
   c.h_res = h_res;
   c.h_out = h_out;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = group_size;
-  c.alpha = 1.f;
-  c.ws = ws;
-  c.ws_bytes = ws_bytes;
-  c.sync = sync;
   return run_gemm(reinterpret_cast<hipStream_t>(stream), c);
 }
 
@@ -1424,26 +778,10 @@ static int gemm_addto_norm_impl(void* stream, int wbits, const void* x, const vo
   DIHIP_REQUIRE(sync != nullptr && h_out && gamma && xnorm, DIHIP_PARAM_ERROR, "fused addto + norm: null pointer");
   if (M == 0) return DIHIP_SUCCESS;
   bool done = false;
-  GemmCall c{};
-  c.wbits = wbits;
-  c.dtype = dtype;
-  c.pro = PRO_PLAIN;
-  c.epi = EPI_ADDTO;
-  c.x = x;
-  c.ldx = K;
+  GemmCall c = make_call(wbits, dtype, PRO_PLAIN, EPI_ADDTO, x, w_packed, sz_packed, nullptr, M, N, K, group_size, ws, ws_bytes, sync);
   c.x_layout = x_layout;
-  c.w0 = w_packed;
-  c.sz0 = sz_packed;
   c.h_res = h_res;
   c.h_out = h_out;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = group_size;
-  c.alpha = 1.f;
-  c.ws = ws;
-  c.ws_bytes = ws_bytes;
-  c.sync = sync;
   c.n_gamma = gamma;
   c.n_eps = eps;
   c.n_out = xnorm;
@@ -1480,21 +818,6 @@ int dihip_fused_gemm_addto_prenorm(void* stream, int wbits, const void* x, const
 
 size_t dihip_rowsq_bytes() { return (size_t)256 * 32 * sizeof(float); }  // one part per workgroup of a producer (<= one per CU)
 
-// can a prenorm GEMM (dual = 0) / SwiGLU pair (dual = 1) of this shape take deferred row norms?  (mirrors run_gemm's dispatch)
-int dihip_prenorm_rowsq_supported(int wbits, int M, int N, int K, int group_size, int dual, int dtype, int x_layout) {
-  static const bool on = !env_off("DIHIP_DEFER_RMSNORM");  // =0: never (A/B; callers then keep the norm launch)
-  if (!on || M <= 4 || M > 32 || dtype != DIHIP_BF16 || (wbits != 4 && wbits != 8) || !gemv_stream_enabled()) return 0;
-  const LowpDims d = lowp_dims(wbits, N, K, group_size);
-  if (K != d.Kp || !(d.group == 0 || d.group % d.KTILE == 0)) return 0;
-  if (x_layout == DIHIP_ACT_FRAG32) {
-    const KslicePlan kp = make_kslice_plan(wbits, M, N, K, group_size, dual != 0);
-    if (kp.ok) return 1;
-    const PanelPlan pp = make_panel_plan(wbits, M, N, K, group_size, dual != 0);
-    if (pp.ok) return pp.nslices > 1 ? 1 : 0;
-  }
-  return dual ? 0 : 1;  // gemv_batch_kernel: plain epilogue only
-}
-
 // LayerNormNoBeta of the f32 hidden rows into FT rows, on its own (the MoE layer feeds four consumers from it)
 int dihip_rmsnorm_rows(void* stream, void* xnorm, const float* h, const void* gamma, float eps, int M, int K, int dtype) {
   DIHIP_REQUIRE(M >= 0 && K > 0 && xnorm && h && gamma, DIHIP_PARAM_ERROR, "rmsnorm_rows: bad argument");
@@ -1510,36 +833,24 @@ int dihip_prenorm_gemm(void* stream, int wbits, const void* xnorm, int x_layout,
                                   dtype, nullptr, 0, 0.f);
 }
 
+// the activations of a prenorm call: normalised rows in either layout, with or without deferred row norms
+static void set_prenorm_input(GemmCall& c, int x_layout, const float* rowsq, int rowsq_parts, float eps) {
+  c.x_layout = x_layout;
+  c.rowsq = rowsq_parts > 0 ? rowsq : nullptr;
+  c.rowsq_parts = rowsq_parts;
+  c.rowsq_eps = eps;
+}
+
 int dihip_prenorm_gemm_rowsq(void* stream, int wbits, const void* xnorm, int x_layout, const void* w_packed, const void* sz_packed,
                              const void* bias, void* y, int M, int N, int K, int group_size, int act, void* ws, size_t ws_bytes,
                              void* sync, int dtype, const float* rowsq, int rowsq_parts, float eps) {
   DIHIP_REQUIRE(dtype == DIHIP_BF16 || dtype == DIHIP_F16, DIHIP_PARAM_ERROR, "fused path: bf16 or f16 activations");
   DIHIP_REQUIRE(x_layout == DIHIP_ACT_ROWMAJOR || x_layout == DIHIP_ACT_FRAG32, DIHIP_PARAM_ERROR, "prenorm gemm: bad x_layout");
   DIHIP_REQUIRE(sync != nullptr && xnorm && y, DIHIP_PARAM_ERROR, "prenorm gemm: null pointer");
-  GemmCall c{};
-  c.wbits = wbits;
-  c.dtype = dtype;
-  c.pro = PRO_PLAIN;
-  c.epi = EPI_STD;
-  c.x = xnorm;
-  c.ldx = K;
-  c.x_layout = x_layout;
-  c.w0 = w_packed;
-  c.sz0 = sz_packed;
+  GemmCall c = make_call(wbits, dtype, PRO_PLAIN, EPI_STD, xnorm, w_packed, sz_packed, y, M, N, K, group_size, ws, ws_bytes, sync);
   c.bias = bias;
-  c.y = y;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = group_size;
   c.act = act;
-  c.alpha = 1.f;
-  c.ws = ws;
-  c.ws_bytes = ws_bytes;
-  c.sync = sync;
-  c.rowsq = rowsq_parts > 0 ? rowsq : nullptr;
-  c.rowsq_parts = rowsq_parts;
-  c.rowsq_eps = eps;
+  set_prenorm_input(c, x_layout, rowsq, rowsq_parts, eps);
   return run_gemm(reinterpret_cast<hipStream_t>(stream), c);
 }
 
@@ -1558,126 +869,14 @@ int dihip_prenorm_swiglu_rowsq(void* stream, int wbits, const void* xnorm, int x
   DIHIP_REQUIRE(x_layout == DIHIP_ACT_ROWMAJOR || x_layout == DIHIP_ACT_FRAG32, DIHIP_PARAM_ERROR, "prenorm swiglu: bad x_layout");
   DIHIP_REQUIRE(y_layout == DIHIP_ACT_ROWMAJOR || y_layout == DIHIP_ACT_FRAG32, DIHIP_PARAM_ERROR, "prenorm swiglu: bad y_layout");
   DIHIP_REQUIRE(sync != nullptr && xnorm && y, DIHIP_PARAM_ERROR, "prenorm swiglu: null pointer");
-  DIHIP_REQUIRE(y_layout == DIHIP_ACT_ROWMAJOR || (M > 4 && batch_kernel_eligible(wbits, M, N, K, group_size)), DIHIP_PARAM_ERROR,
-                "prenorm swiglu: FRAG32 output needs the small-batch kernel (4 < M <= 32, K a multiple of the k-tile)");
-  GemmCall c{};
-  c.wbits = wbits;
-  c.dtype = dtype;
-  c.pro = PRO_PLAIN;
-  c.epi = EPI_SWIGLU;
-  c.x = xnorm;
-  c.ldx = K;
-  c.x_layout = x_layout;
-  c.y_layout = y_layout;
-  c.w0 = wg_packed;
-  c.sz0 = szg_packed;
+  DIHIP_REQUIRE(y_layout == DIHIP_ACT_ROWMAJOR || (M > GEMV_STREAM_MAX_M && lowp_frag_served(wbits, dtype, M, N, K, group_size, true)),
+                DIHIP_PARAM_ERROR, "prenorm swiglu: FRAG32 output needs the small-batch kernel (4 < M <= 32, K a multiple of the k-tile)");
+  GemmCall c = make_call(wbits, dtype, PRO_PLAIN, EPI_SWIGLU, xnorm, wg_packed, szg_packed, y, M, N, K, group_size, ws, ws_bytes, sync);
   c.w1 = wu_packed;
   c.sz1 = szu_packed;
-  c.y = y;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = group_size;
-  c.alpha = 1.f;
-  c.ws = ws;
-  c.ws_bytes = ws_bytes;
-  c.sync = sync;
-  c.rowsq = rowsq_parts > 0 ? rowsq : nullptr;
-  c.rowsq_parts = rowsq_parts;
-  c.rowsq_eps = eps;
+  c.y_layout = y_layout;
+  set_prenorm_input(c, x_layout, rowsq, rowsq_parts, eps);
   return run_gemm(reinterpret_cast<hipStream_t>(stream), c);
-}
-
-
-// ---- unquantised 16-bit weights (lm_head / dense Gemm), same kernel family ----------------------
-size_t dihip_dense_packed_weight_bytes(int N, int K) {
-  if (N <= 0 || K <= 0) return 0;
-  const LowpDims d = lowp_dims(16, N, K, -1);
-  return (size_t)d.NTILES * d.KT * 64 * 16;
-}
-
-int dihip_dense_pack(void* stream, const void* w_kn, int N, int K, int dtype, void* w_packed) {
-  DIHIP_REQUIRE(N > 0 && K > 0 && w_kn && w_packed, DIHIP_PARAM_ERROR, "dense_pack: bad argument");
-  DIHIP_REQUIRE(dtype == DIHIP_BF16 || dtype == DIHIP_F16, DIHIP_PARAM_ERROR, "dense_pack: dtype");
-  const LowpDims d = lowp_dims(16, N, K, -1);
-  const size_t total = (size_t)d.NTILES * d.KT * 64 * 4;
-  hipLaunchKernelGGL(pack_w16_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), (const uint16_t*)w_kn, (uint32_t*)w_packed, N, K, d.KT,
-                     d.NTILES);
-  return launch_status();
-}
-
-size_t dihip_dense_workspace_bytes(int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const GemmPlan p = make_plan(16, M, N, K, -1, false);
-  return p.slab_bytes + GEMM_SYNC_BYTES + (size_t)M * K * 2 + 512;
-}
-
-int dihip_gemm_a16w16(void* stream, const void* x, const void* w_packed, const void* bias, const void* residual,
-                      void* y, int M, int N, int K, int act, float alpha, void* ws, size_t ws_bytes, void* sync,
-                      int dtype) {
-  GemmCall c{};
-  c.wbits = 16;
-  c.dtype = dtype;
-  c.pro = PRO_PLAIN;
-  c.epi = EPI_STD;
-  c.x = x;
-  c.ldx = K;
-  c.w0 = w_packed;
-  c.bias = bias;
-  c.residual = residual;
-  c.y = y;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = -1;
-  c.act = act;
-  c.alpha = alpha;
-  c.ws = ws;
-  c.ws_bytes = ws_bytes;
-  c.sync = sync;
-  return run_gemm(reinterpret_cast<hipStream_t>(stream), c);
-}
-
-int dihip_lm_head(void* stream, float* logits, const float* h, const void* gamma, float eps, const void* w_packed,
-                  int M, int N, int K, void* ws, size_t ws_bytes, void* sync, int dtype) {
-  DIHIP_REQUIRE(dtype == DIHIP_BF16 || dtype == DIHIP_F16, DIHIP_PARAM_ERROR, "lm_head: dtype");
-  DIHIP_REQUIRE(logits && h && w_packed && sync, DIHIP_PARAM_ERROR, "lm_head: null pointer");
-  if (M == 0) return DIHIP_SUCCESS;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GemmCall c{};
-  c.wbits = 16;
-  c.dtype = dtype;
-  c.epi = EPI_ADDTO;
-  c.w0 = w_packed;
-  c.h_res = nullptr;
-  c.h_out = logits;
-  c.M = M;
-  c.N = N;
-  c.K = K;
-  c.group_size = -1;
-  c.alpha = 1.f;
-  c.sync = sync;
-  c.ldx = K;
-  if (gamma != nullptr && M <= 4) {
-    c.pro = PRO_RMSNORM;
-    c.x = h;
-    c.gamma = gamma;
-    c.eps = eps;
-    c.ws = ws;
-    c.ws_bytes = ws_bytes;
-  } else {
-    DIHIP_REQUIRE(gamma != nullptr, DIHIP_PARAM_ERROR, "lm_head: needs gamma");
-    void* xn;
-    size_t left;
-    int st = norm_to_ws(s, h, gamma, eps, M, K, dtype, ws, ws_bytes, 16, N, -1, false, &xn, &left, &c.x_layout);
-    if (st) return st;
-    c.pro = PRO_PLAIN;
-    c.x = xn;
-    c.ws = ws;
-    c.ws_bytes = left;
-  }
-  return run_gemm(s, c);
 }
 
 }  // extern "C"

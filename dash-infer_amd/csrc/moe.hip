@@ -18,12 +18,10 @@
 
 #include "device_utils.h"
 #include "gemm_lowp_kernel.hpp"  // mfma16
+#include "gemm_lowp_plan.hpp"    // run_gemv_slots
 
 namespace dihip {
 
-int run_gemv_slots(hipStream_t stream, int wbits, int epi, const void* x, int ldx, int x_div, const void* w0, const void* sz0,
-                   const void* w1, const void* sz1, void* y, int N, int K, int group_size, const int* slot_expert, int nslots,
-                   const int* group_rows, const int* group_nrows);
 constexpr int MOE_EPI_STD = 0, MOE_EPI_SWIGLU = 1;  // EPI_STD / EPI_SWIGLU of gemm_lowp_kernel.hpp
 
 struct ScoreIdx {

@@ -71,6 +71,18 @@ int dihip_device_info(int* num_cus, int* lds_bytes_per_cu, char* name, size_t na
  *    take the packed buffers.
  * ========================================================================================== */
 
+/* Six kernel families serve these calls (gemv_stream, gemm_kslice, gemm_panel, gemv_batch, gemm_prefill, gemm_lowp); ONE
+ * route decision (csrc/gemm_lowp_plan.hpp, plan_gemm) picks the family, the specialisation and the grid from the call and
+ * the CU count, and every query below (dihip_gemm_lowp_prefers_frag, dihip_prenorm_rowsq_supported, the workspace sizes,
+ * dihip_debug_gemm_route) is derived from it.  The shape-only queries assume 16-byte aligned pointers, row stride K and a
+ * workspace of dihip_gemm_lowp_workspace_bytes().  Environment (A/B and diagnostics; each read in one place):
+ *   DIHIP_GEMV_STREAM=0         no decode / small-batch kernels: everything on gemm_prefill / gemm_lowp
+ *   DIHIP_GEMM_KSLICE=0 | 2     never / every eligible shape on gemm_kslice (read per call)
+ *   DIHIP_GEMM_PANEL=0          no gemm_panel (gemv_batch serves its shapes)
+ *   DIHIP_GEMM_PREFILL=0        no gemm_prefill (gemm_lowp serves the context phase)
+ *   DIHIP_PREFILL_TAIL_SPLIT=0  gemm_prefill without the K split of its last round
+ *   DIHIP_DEFER_RMSNORM=0       dihip_prenorm_rowsq_supported answers 0 */
+
 /* bytes of the packed weight / packed (scale,zero) buffers for a [K,N] weight */
 size_t dihip_gemm_lowp_packed_weight_bytes(int wbits, int N, int K);
 size_t dihip_gemm_lowp_packed_sz_bytes(int N, int K, int group_size);
@@ -702,6 +714,23 @@ int dihip_debug_gemv_plan(int wbits, int M, int N, int K, int group_size, int du
 /* split plan of the decode attention for a shape on `num_cus` CUs (0: this device's count, 256 without a device) */
 int dihip_debug_attn_plan(int batch, int n_heads, int n_groups, int max_seq_len, int kv_mode, int dtype, int num_cus,
                           int* nsplits, int* mfma);
+/* The route of a weight-only GEMM call (section 1): the kernel family that serves it, the template specialisation and the
+ * launch.  pro: 0 plain, 1 RMSNorm prologue; epi: 0 std, 1 SwiGLU pair, 2 f32 add-to; x [M, K] with row stride K; `flags`
+ * describe what else the route depends on (0: aligned pointers, ample workspace, a sync buffer).  out[DIHIP_ROUTE_FIELDS]:
+ *   0 family (0 not served, 1 gemv_stream, 2 gemm_kslice, 3 gemm_panel, 4 gemv_batch, 5 gemm_prefill, 6 gemm_lowp)
+ *   1 MT (gemv_stream: MR)  2 NT  3 PRO  4 EPI  5 GPT  6 RS      template arguments (0 where the family has none)
+ *   7-9 grid x, y, z (workgroups)  10 threads  11 dynamic LDS bytes  12 split-K slab bytes  13 CU count planned for
+ *   14 norm of an add-to call: 0 own launch, 1 rides on the slab reduction, 2 deferred (row partials)
+ *   15 status the call would return (DIHIP_SUCCESS, or why it is not served) */
+#define DIHIP_ROUTE_ROWSQ 1      /* deferred row norms handed in (dihip_prenorm_*_rowsq) */
+#define DIHIP_ROUTE_NORM 2       /* dihip_fused_gemm_addto_norm */
+#define DIHIP_ROUTE_PRENORM 4    /* dihip_fused_gemm_addto_prenorm, rowsq of dihip_rowsq_bytes() */
+#define DIHIP_ROUTE_NO_WS 8      /* no workspace */
+#define DIHIP_ROUTE_NO_SYNC 16   /* sync == NULL */
+#define DIHIP_ROUTE_UNALIGNED 32 /* x / gamma / ws not 16-byte aligned */
+#define DIHIP_ROUTE_FIELDS 16
+int dihip_debug_gemm_route(int wbits, int dtype, int pro, int epi, int M, int N, int K, int group_size, int x_layout,
+                           int y_layout, int flags, long long* out);
 
 #ifdef __cplusplus
 }
