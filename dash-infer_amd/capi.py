@@ -63,6 +63,9 @@ _SIGS = {
     "dihip_moe_experts": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, sz, i32]),
     "dihip_moe_experts_ex": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, sz, i32, i32]),
     "dihip_moe_route_grouped": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, sz]),
+    "dihip_moe_gemm_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "dihip_moe_sort_slots": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, sz]),
+    "dihip_moe_experts_gemm": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, i32, i32]),
     "dihip_moe_combine": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32]),
     "dihip_moe_router_gate": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32]),
     "dihip_act_frag_bytes": (sz, [i32, i32]),

@@ -521,6 +521,44 @@ int run_gemv_slots(hipStream_t stream, int wbits, int epi, const void* x, int ld
   return DIHIP_SUCCESS;
 }
 
+int prefill_grouped_col_blocks(int N, bool dual) {
+  const int tpb = dual ? PF_WN * PF_CW / 2 : PF_WN * PF_CW;
+  return ((N + 15) / 16 + tpb - 1) / tpb;
+}
+
+int run_prefill_grouped(hipStream_t stream, int wbits, int epi, const void* x, int ldx, int x_div, const void* w0, const void* sz0,
+                        const void* w1, const void* sz1, void* y, int N, int K, int group_size, const int* tiles, const int* ntiles,
+                        const int* sorted_slot, int max_tiles) {
+  const LowpDims d = lowp_dims(wbits, N, K, group_size);
+  DIHIP_REQUIRE(K == d.Kp && (d.group == 0 || d.group % d.KTILE == 0) && ldx % 8 == 0, DIHIP_PARAM_ERROR,
+                "moe: K = %d must be a multiple of the k-tile (%d) and groups whole k-tiles", K, d.KTILE);
+  PrefillArgs g{};
+  fill_operands(g, x, w0, sz0, w1, sz1, y, 0, N, d);
+  g.ldx = ldx;
+  g.ktpg = d.ktpg;
+  g.col_blocks = prefill_grouped_col_blocks(N, epi == EPI_SWIGLU);
+  g.tail_cb = g.col_blocks;  // no tail split
+  g.ksplit = 1;
+  g.g_tiles = tiles;
+  g.g_ntiles = ntiles;
+  g.g_sorted = sorted_slot;
+  g.g_max_tiles = max_tiles;
+  g.g_x_div = x_div;
+  g.g_w_estride = (size_t)d.NTILES * d.KT * 64;
+  g.g_sz_estride = (size_t)d.NTILES * g.Gp * 16;
+  DIHIP_REQUIRE((size_t)max_tiles * g.col_blocks <= 0x7FFFFFFFu, DIHIP_EXCEED_LIMIT_ERROR, "moe: %d row tiles x %d column blocks exceed one launch",
+                max_tiles, g.col_blocks);
+  const bool gpt = d.group == d.KTILE;  // every k-tile is one quantisation group
+  hipError_t e = hipErrorInvalidValue;
+#define GROUPED_GO(W_, EPI_, G_) \
+  if (wbits == W_ && epi == EPI_ && (int)gpt == G_) e = launch_gemm_prefill_grouped<W_, DIHIP_BF16, EPI_, G_>(g, stream);
+  GROUPED_GO(8, EPI_SWIGLU, 0) GROUPED_GO(8, EPI_STD, 0) GROUPED_GO(8, EPI_SWIGLU, 1) GROUPED_GO(8, EPI_STD, 1)
+  GROUPED_GO(4, EPI_SWIGLU, 0) GROUPED_GO(4, EPI_STD, 0) GROUPED_GO(4, EPI_SWIGLU, 1) GROUPED_GO(4, EPI_STD, 1)
+#undef GROUPED_GO
+  DIHIP_REQUIRE(e == hipSuccess, DIHIP_RUNTIME_ERROR, "moe: grouped expert GEMM launch failed: %s", hipGetErrorString(e));
+  return DIHIP_SUCCESS;
+}
+
 }  // namespace dihip
 
 using namespace dihip;

@@ -170,6 +170,14 @@ bool lowp_frag_served(int wbits, int dtype, int M, int N, int K, int group_size,
 int run_gemv_slots(hipStream_t stream, int wbits, int epi, const void* x, int ldx, int x_div, const void* w0, const void* sz0,
                    const void* w1, const void* sz1, void* y, int N, int K, int group_size, const int* slot_expert, int nslots,
                    const int* group_rows, const int* group_nrows);
+// One launch of the context-phase GEMM over the expert-sorted row tiles of a prompt (mixture-of-experts, moe.hip:
+// gemm_prefill_kernel<.., GROUPED>): tile t = {expert, first sorted position, rows <= 128} of `tiles`, its rows are the slots
+// sorted_slot[first ..], slot s reads activation row s / x_div and writes row s.  The grid is max_tiles x column blocks;
+// workgroups past *ntiles (device memory) exit.  bf16, STD / SwiGLU, no tail split.
+int run_prefill_grouped(hipStream_t stream, int wbits, int epi, const void* x, int ldx, int x_div, const void* w0, const void* sz0,
+                        const void* w1, const void* sz1, void* y, int N, int K, int group_size, const int* tiles, const int* ntiles,
+                        const int* sorted_slot, int max_tiles);
+int prefill_grouped_col_blocks(int N, bool dual);  // column blocks of such a launch (dual: SwiGLU, 128 output columns each)
 // The decode GEMV's plan for ONE row as the workgroups of ANOTHER launch run it (decode_attn_block.hip): the K split (WK, kcut)
 // and the wave grid are those of the stand-alone launch -- the sums are then bit-identical to it -- while the column tiles are dealt
 // over `nblocks` workgroups (block b owns tiles b, b + nblocks, ...).  Fills the shape / plan fields of *g (pointers are the

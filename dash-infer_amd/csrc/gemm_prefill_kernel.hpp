@@ -20,6 +20,9 @@
 //   * epilogues as everywhere: STD (alpha, bias, UnaryType activation, FT residual), SwiGLU over a gate / up pair (a wave's two
 //     column tiles are then the SAME 16 columns of the two matrices: 128 output columns per workgroup), f32 hidden-stream update.
 //
+// GROUPED (template parameter, default off): the same kernel over the expert-sorted row tiles of a mixture-of-experts prompt -- rows
+// gathered and scattered through the slot sort's tables, the weight base offset by the tile's expert (moe.hip, run_prefill_grouped).
+//
 // Host contract (gemm_lowp.hip: run_gemm): bf16 / f16 activations row-major with ldx % 8 == 0, 16-byte aligned; K a multiple of
 // the k-tile; group_size a multiple of the k-tile or per-channel.  Rows >= M are clamped on load and masked on store.
 //
@@ -96,16 +99,28 @@ struct PrefillArgs {
   int ksplit;
   float* slab;  // [tail tile][ksplit][PF_BM][256] f32
   unsigned long long* trace;  // per-wave cycle stamps (library built with -DDIHIP_PF_TRACE, tools/prefill_trace.py)
+  // GROUPED (mixture-of-experts context phase, moe.hip: dihip_moe_experts_gemm): a workgroup's 128 rows are ONE tile of the slot
+  // sort -- rows of one expert, gathered through sorted_slot -- and its weights are that expert's of a stack of equally shaped
+  // packed matrices.  Unused (null / 0) by the dense instantiations, whose code does not read them.
+  const int* g_tiles;    // [tile][4] {expert, first sorted position, rows, 0}
+  const int* g_ntiles;   // tiles the sort made (device side: workgroups past it exit)
+  const int* g_sorted;   // sorted position -> slot
+  int g_max_tiles;       // the host's bound: the grid is g_max_tiles x col_blocks
+  int g_x_div;           // slot s reads activation row s / g_x_div and writes output row s
+  size_t g_w_estride;    // u32x4 per expert
+  size_t g_sz_estride;   // u32 per expert
 };
 
-template <int WBITS>
+template <int WBITS, bool GROUPED = false>
 constexpr size_t prefill_lds_bytes() {
-  // 2 x A tile (PF_TR x KSTEPS fragments of 1 KiB) + 2 x 128 row sums
-  return (size_t)2 * PF_TR * WTraits<WBITS>::KSTEPS * 1024 + 2 * PF_BM * sizeof(float);
+  // 2 x A tile (PF_TR x KSTEPS fragments of 1 KiB) + 2 x 128 row sums (+ GROUPED: the tile's 128 slot indices)
+  return (size_t)2 * PF_TR * WTraits<WBITS>::KSTEPS * 1024 + 2 * PF_BM * sizeof(float) + (GROUPED ? PF_BM * sizeof(int) : 0);
 }
 
 // (GPT -- one k-tile per quantisation group -- is a compile-time copy of the same code: the group test folds away)
-template <int WBITS, int FT, int EPI, int GPT>
+// (GROUPED -- the expert-sorted row tiles of the mixture-of-experts context phase -- differs in where a row comes from and goes
+// to, and in the weight base; the k loop is the same code)
+template <int WBITS, int FT, int EPI, int GPT, bool GROUPED = false>
 __global__ __launch_bounds__(PF_THREADS, 2) void gemm_prefill_kernel(const PrefillArgs a) {
   using WT = WTraits<WBITS>;
   using EX = ExpandV<WBITS, FT>;
@@ -121,10 +136,21 @@ __global__ __launch_bounds__(PF_THREADS, 2) void gemm_prefill_kernel(const Prefi
   const int ni = lane & 15, kb = lane >> 4;
   const int wm = wave / PF_WN, wn = wave - wm * PF_WN;  // this wave's place in the PF_WM x PF_WN grid
   // consecutive workgroups share a column block (its weights stay hot in the L2s) and walk the rows
-  const int mblocks = (a.M + PF_BM - 1) / PF_BM;
+  // (GROUPED: the row blocks are the sort's tiles -- those of one expert are neighbours and share its column block's weights)
+  const int mblocks = GROUPED ? a.g_max_tiles : (a.M + PF_BM - 1) / PF_BM;
   int cb = blockIdx.x / mblocks, mb = blockIdx.x - cb * mblocks;
+  int g_first = 0, g_rows = 0;  // GROUPED: this tile's first sorted position and its row count
+  size_t g_woff = 0, g_szoff = 0;
+  if constexpr (GROUPED) {
+    if (mb >= *a.g_ntiles) return;  // (uniform) the grid is the host's upper bound
+    const int e = a.g_tiles[mb * 4];
+    g_first = a.g_tiles[mb * 4 + 1];
+    g_rows = a.g_tiles[mb * 4 + 2];
+    g_woff = (size_t)e * a.g_w_estride;
+    g_szoff = (size_t)e * a.g_sz_estride;
+  }
   int kt0 = 0, kt1 = a.KT, split_part = -1, split_tile = 0;  // this workgroup's k-tiles; tail split: its part and tile
-  if (cb >= a.tail_cb) {  // (uniform) mb fastest, then the K part, then the column block: the 16 row blocks of a part share its weights
+  if (!GROUPED && cb >= a.tail_cb) {  // (uniform) mb fastest, then the K part, then the column block: the 16 row blocks of a part share its weights
     const int idx = (int)blockIdx.x - a.tail_cb * mblocks;
     mb = idx % mblocks;
     const int t = idx / mblocks;
@@ -151,12 +177,21 @@ __global__ __launch_bounds__(PF_THREADS, 2) void gemm_prefill_kernel(const Prefi
     tile_ok[c] = t < a.NTILES;
     tile[c] = min(t, a.NTILES - 1);
     const bool second = DUAL && c >= HCW;
-    wp[c] = (second ? a.w1 : a.w0) + (size_t)tile[c] * a.KT * 64 + lane;
-    szp[c] = (second ? a.sz1 : a.sz0) + (size_t)tile[c] * a.Gp * 16 + ni;
+    wp[c] = (second ? a.w1 : a.w0) + g_woff + (size_t)tile[c] * a.KT * 64 + lane;
+    szp[c] = (second ? a.sz1 : a.sz0) + g_szoff + (size_t)tile[c] * a.Gp * 16 + ni;
   }
 
   // ---- A staging: wave w stages row tile w (all KSTEPS fragments of the k-tile): lane (kb, r) <- 16 bytes of row m0 + 16 w + r
-  const int arow = min(m0 + wave * 16 + ni, a.M - 1);  // rows past M re-read the last row (masked on store)
+  int arow;
+  if constexpr (GROUPED) {  // gather: the row's slot; rows past the tile's count re-read its last row (masked on store)
+    int* gslot = reinterpret_cast<int*>(smem + 2 * ABYTES + 2 * PF_BM * sizeof(float));  // [PF_BM] slot of every row, -1: none
+    const int r = wave * 16 + ni;
+    const int slot = a.g_sorted[g_first + min(r, g_rows - 1)];
+    if (kb == 0) gslot[r] = r < g_rows ? slot : -1;  // read in the epilogue (barriers in between)
+    arow = slot / a.g_x_div;
+  } else {
+    arow = min(m0 + wave * 16 + ni, a.M - 1);  // rows past M re-read the last row (masked on store)
+  }
   const char* xrow = reinterpret_cast<const char*>(a.x) + ((size_t)arow * a.ldx + kb * 8) * 2;
   u32x4_t areg[KSTEPS];
   u32x4_t wreg[PF_CW];
@@ -316,10 +351,16 @@ __global__ __launch_bounds__(PF_THREADS, 2) void gemm_prefill_kernel(const Prefi
   // ---- epilogue: lane (kb, ni) holds rows rt * 16 + kb * 4 + r of column tile c, column ni --------------------
 #pragma unroll
   for (int rt = 0; rt < PF_RT; ++rt) {
+    int gs[4] = {0, 0, 0, 0};
+    if constexpr (GROUPED) {  // scatter: the rows' slots
+      const int* gslot = reinterpret_cast<const int*>(smem + 2 * ABYTES + 2 * PF_BM * sizeof(float));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gs[r] = gslot[(wm * PF_RT + rt) * 16 + kb * 4 + r];
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int m = m0 + (wm * PF_RT + rt) * 16 + kb * 4 + r;
-      if (m >= a.M) continue;
+      const int m = GROUPED ? gs[r] : m0 + (wm * PF_RT + rt) * 16 + kb * 4 + r;
+      if (GROUPED ? m < 0 : m >= a.M) continue;
       if constexpr (DUAL) {
 #pragma unroll
         for (int c = 0; c < HCW; ++c) {
@@ -388,6 +429,9 @@ __global__ __launch_bounds__(256) void gemm_prefill_tail_reduce_kernel(const Pre
 
 template <int WBITS, int FT, int EPI, int GPT>
 hipError_t launch_gemm_prefill(const PrefillArgs& a, int blocks, hipStream_t stream);
+// the GROUPED form (gemm_prefill_grouped_inst_*.hip): a.g_max_tiles x a.col_blocks workgroups, no tail split
+template <int WBITS, int FT, int EPI, int GPT>
+hipError_t launch_gemm_prefill_grouped(const PrefillArgs& a, hipStream_t stream);
 
 #define DIHIP_DEFINE_PREFILL_LAUNCH(WBITS, FT, EPI, GPT)                                                           \
   template <>                                                                                                      \
@@ -414,6 +458,36 @@ hipError_t launch_gemm_prefill(const PrefillArgs& a, int blocks, hipStream_t str
     }                                                                                                              \
     return hipGetLastError();                                                                                      \
   }
+
+// GROUPED launch: the same LDS grant (the instantiation is another kernel: its own per-device mask), one launch, no tail pass
+#define DIHIP_DEFINE_PREFILL_GROUPED_LAUNCH(WBITS, FT, EPI, GPT)                                                   \
+  template <>                                                                                                      \
+  hipError_t launch_gemm_prefill_grouped<WBITS, FT, EPI, GPT>(const PrefillArgs& a, hipStream_t s) {               \
+    auto kern = gemm_prefill_kernel<WBITS, FT, EPI, GPT, true>;                                                    \
+    constexpr size_t lds = prefill_lds_bytes<WBITS, true>();                                                       \
+    if (lds > 64 * 1024) {                                                                                         \
+      static std::atomic<unsigned> granted_mask[4];                                                                \
+      int dev = 0;                                                                                                 \
+      if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();                                              \
+      const unsigned bit = 1u << (dev & 31);                                                                       \
+      std::atomic<unsigned>* word = dev >= 0 && dev < 128 ? &granted_mask[dev >> 5] : nullptr;                     \
+      if (!word || !(word->load(std::memory_order_acquire) & bit)) {                                               \
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                              \
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
+        if (e != hipSuccess) return e;                                                                             \
+        if (word) word->fetch_or(bit, std::memory_order_release);                                                  \
+      }                                                                                                            \
+    }                                                                                                              \
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.g_max_tiles * (unsigned)a.col_blocks), dim3(PF_THREADS), lds, s, a); \
+    return hipGetLastError();                                                                                      \
+  }
+
+// bf16 only (the mixture-of-experts path): {per-channel / multi-k-tile groups, one k-tile per group} x {SwiGLU, STD}
+#define DIHIP_DEFINE_PREFILL_GROUPED_LAUNCH_SET(WBITS)                     \
+  DIHIP_DEFINE_PREFILL_GROUPED_LAUNCH(WBITS, DIHIP_BF16, EPI_STD, 0)       \
+  DIHIP_DEFINE_PREFILL_GROUPED_LAUNCH(WBITS, DIHIP_BF16, EPI_STD, 1)       \
+  DIHIP_DEFINE_PREFILL_GROUPED_LAUNCH(WBITS, DIHIP_BF16, EPI_SWIGLU, 0)    \
+  DIHIP_DEFINE_PREFILL_GROUPED_LAUNCH(WBITS, DIHIP_BF16, EPI_SWIGLU, 1)
 
 #define DIHIP_DEFINE_PREFILL_LAUNCH_SET(WBITS, FT)          \
   DIHIP_DEFINE_PREFILL_LAUNCH(WBITS, FT, EPI_STD, 0)        \

@@ -14,6 +14,8 @@
 // of the decode GEMV kernel per projection covers all (token, expert-rank) slots: gridDim.y = slots, the slot's
 // expert index offsets the weight base (gemv_stream_kernel<..., SLOT = true>), SwiGLU is fused into the gate/up
 // launch, and a small kernel applies the routing weights.  No host work per step: routing results stay on the device.
+// A prompt's rows are another shape: hundreds of rows per expert.  dihip_moe_experts_gemm (below: "context phase") sorts the slots by
+// expert and runs one grouped launch of the context-phase MFMA GEMM per projection (gemm_prefill_kernel<.., GROUPED>).
 #include <algorithm>
 
 #include "device_utils.h"
@@ -227,6 +229,87 @@ __global__ __launch_bounds__(1024) void moe_route_group_kernel(float* __restrict
   group_slots(group_expert, group_rows, group_nrows, experts, T * top_k, L);
 }
 
+// ---- context phase: slot sort for the grouped expert GEMM (gemm_prefill_kernel<.., GROUPED>) ----------------------------------
+// A stable counting sort of the (token, expert-rank) slots by expert, for any slot count, in three launches with nothing read
+// back: (1) every workgroup counts the experts of its chunk of MOE_SORT_CHUNK slots; (2) one workgroup turns the [chunk][expert]
+// counts into each chunk's first position per expert, and writes expert_offset and the table of row tiles (<= 128 slots of one
+// expert, the grouped GEMM's workgroup tile) with its count; (3) every workgroup places its slots: position = its chunk's first
+// position for the expert + the slot's rank among the chunk's earlier slots of that expert.  The only atomics are integer counts
+// in LDS (any arrival order gives the same count); positions come from ranks, so the tables are the same bytes run to run.
+// Slots with expert < 0 (another rank's) or >= E appear nowhere.
+constexpr int MOE_SORT_CHUNK = 1024;  // slots per workgroup of passes 1 and 3 (one per thread)
+constexpr int MOE_TILE_ROWS = 128;    // PF_BM of gemm_prefill_kernel.hpp
+
+__global__ __launch_bounds__(MOE_SORT_CHUNK) void moe_sort_count_kernel(int* __restrict__ chunk_cnt, const int* __restrict__ experts,
+                                                                        int nslots, int E) {
+  __shared__ int cnt[256];
+  const int tid = threadIdx.x, s = blockIdx.x * MOE_SORT_CHUNK + tid;
+  if (tid < 256) cnt[tid] = 0;
+  __syncthreads();
+  const int e = s < nslots ? experts[s] : -1;
+  if (e >= 0 && e < E) atomicAdd(&cnt[e], 1);
+  __syncthreads();
+  if (tid < E) chunk_cnt[(size_t)blockIdx.x * E + tid] = cnt[tid];
+}
+
+// one workgroup of 256 threads (thread e = expert e): chunk_cnt becomes, in place, the first sorted position of (chunk, expert)
+__global__ __launch_bounds__(256) void moe_sort_scan_kernel(int* __restrict__ chunk_cnt, int* __restrict__ expert_offset,
+                                                            int* __restrict__ tiles, int* __restrict__ ntiles, int nchunks, int E) {
+  __shared__ int tot[256], off[257], toff[257];
+  const int tid = threadIdx.x;
+  int n = 0;
+  if (tid < E)
+    for (int c = 0; c < nchunks; ++c) n += chunk_cnt[(size_t)c * E + tid];
+  tot[tid] = n;
+  __syncthreads();
+  if (tid == 0) {  // E <= 256 entries: a serial scan is shorter than its barriers
+    int o = 0, t = 0;
+    for (int e = 0; e < E; ++e) {
+      off[e] = o;
+      toff[e] = t;
+      o += tot[e];
+      t += (tot[e] + MOE_TILE_ROWS - 1) / MOE_TILE_ROWS;
+    }
+    off[E] = o;
+    toff[E] = t;
+    *ntiles = t;
+  }
+  __syncthreads();
+  for (int e = tid; e <= E; e += 256) expert_offset[e] = off[e];
+  if (tid < E) {
+    int run = off[tid];
+    for (int c = 0; c < nchunks; ++c) {
+      const int v = chunk_cnt[(size_t)c * E + tid];
+      chunk_cnt[(size_t)c * E + tid] = run;
+      run += v;
+    }
+  }
+  for (int e = 0; e < E; ++e) {  // (uniform) the expert's tiles, dealt over the threads
+    const int nt = toff[e + 1] - toff[e];
+    for (int j = tid; j < nt; j += 256) {
+      int* t = tiles + (size_t)(toff[e] + j) * 4;
+      t[0] = e;
+      t[1] = off[e] + j * MOE_TILE_ROWS;
+      t[2] = min(MOE_TILE_ROWS, tot[e] - j * MOE_TILE_ROWS);
+      t[3] = 0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(MOE_SORT_CHUNK) void moe_sort_place_kernel(int* __restrict__ sorted_slot, const int* __restrict__ chunk_first,
+                                                                        const int* __restrict__ experts, int nslots, int E) {
+  __shared__ int ex[MOE_SORT_CHUNK];
+  const int tid = threadIdx.x, s = blockIdx.x * MOE_SORT_CHUNK + tid;
+  int e = s < nslots ? experts[s] : -1;
+  if (e >= E) e = -1;
+  ex[tid] = e;
+  __syncthreads();
+  if (e < 0) return;
+  int r = 0;  // rank among the chunk's earlier slots of the expert (its order is kept: stable)
+  for (int j = 0; j < tid; ++j) r += ex[j] == e ? 1 : 0;
+  sorted_slot[chunk_first[(size_t)blockIdx.x * E + e] + r] = s;
+}
+
 // finalize-routing + the layer tail in one pass (moe_finalize_kernel's sum, rounded to FT like its output tensor, then
 // moe_shared_combine_kernel's expression): bit-identical to the two launches
 template <int FT>
@@ -381,7 +464,43 @@ MoeWs moe_ws_layout(void* ws, size_t slots, int hidden, int proj) {
   w.group_nrows = w.group_rows + slots * 4;
   return w;
 }
-constexpr size_t MOE_GROUP_MAX_SLOTS = MOE_GROUP_LDS_SLOTS;  // the grouping pass is ONE workgroup with the slot list in LDS
+constexpr size_t MOE_GROUP_MAX_SLOTS = MOE_GROUP_LDS_SLOTS;
+// dihip_moe_experts_gemm: the block's workspace above, then (256-byte aligned) the slot sort's tables
+constexpr size_t MOE_GEMM_MAX_SLOTS = (size_t)1 << 20;  // stated in dashinfer_hip.h
+struct MoeSortWs {
+  int* expert_offset;  // [E + 1]
+  int* ntiles;         // [1]
+  int* sorted_slot;    // [slots]
+  int* tiles;          // [max_tiles][4] {expert, first sorted position, rows, 0}
+  int* chunk_first;    // [chunks][E]
+  int max_tiles, nchunks;
+  size_t bytes;        // of the tables
+};
+MoeSortWs moe_sort_layout(char* base, size_t slots, int E) {
+  MoeSortWs t;
+  t.max_tiles = (int)((slots + MOE_TILE_ROWS - 1) / MOE_TILE_ROWS) + E;  // every expert may end in one part-filled tile
+  t.nchunks = (int)((slots + MOE_SORT_CHUNK - 1) / MOE_SORT_CHUNK);
+  const size_t head = ((size_t)(E + 2) * sizeof(int) + 255) / 256 * 256;
+  const size_t sorted = (slots * sizeof(int) + 255) / 256 * 256;
+  const size_t tiles = (size_t)t.max_tiles * 4 * sizeof(int);  // a multiple of 16
+  t.expert_offset = reinterpret_cast<int*>(base);
+  t.ntiles = t.expert_offset + E + 1;
+  t.sorted_slot = reinterpret_cast<int*>(base + head);
+  t.tiles = reinterpret_cast<int*>(base + head + sorted);
+  t.chunk_first = reinterpret_cast<int*>(base + head + sorted + tiles);
+  t.bytes = head + sorted + tiles + (size_t)t.nchunks * E * sizeof(int);
+  return t;
+}
+size_t moe_sort_base(int num_tokens, int top_k, int hidden, int proj) {
+  return (dihip_moe_workspace_bytes(num_tokens, top_k, hidden, proj) + 255) / 256 * 256;
+}
+// the three launches of the slot sort (arguments checked by the callers)
+void launch_moe_sort(hipStream_t s, const MoeSortWs& t, const int32_t* experts, size_t slots, int E) {
+  hipLaunchKernelGGL(moe_sort_count_kernel, dim3(t.nchunks), dim3(MOE_SORT_CHUNK), 0, s, t.chunk_first, experts, (int)slots, E);
+  hipLaunchKernelGGL(moe_sort_scan_kernel, dim3(1), dim3(256), 0, s, t.chunk_first, t.expert_offset, t.tiles, t.ntiles, t.nchunks, E);
+  hipLaunchKernelGGL(moe_sort_place_kernel, dim3(t.nchunks), dim3(MOE_SORT_CHUNK), 0, s, t.sorted_slot, t.chunk_first, experts, (int)slots, E);
+}
+  // the grouping pass is ONE workgroup with the slot list in LDS
 }  // namespace
 
 int dihip_moe_route_grouped(void* stream, const void* router_logits, int num_tokens, int num_experts, int top_k, float* scores,
@@ -463,6 +582,68 @@ int dihip_moe_experts(void* stream, int wbits, const void* x, const int32_t* exp
                               top_k, hidden, proj, group_size, out, ws, ws_bytes, dtype, 0);
 }
 
+size_t dihip_moe_gemm_workspace_bytes(int num_tokens, int top_k, int num_local_experts, int hidden, int proj) {
+  if (num_tokens <= 0 || top_k <= 0 || num_local_experts <= 0 || hidden <= 0 || proj <= 0) return 0;
+  return moe_sort_base(num_tokens, top_k, hidden, proj) + moe_sort_layout(nullptr, (size_t)num_tokens * top_k, num_local_experts).bytes;
+}
+
+int dihip_moe_sort_slots(void* stream, const int32_t* experts, int num_tokens, int top_k, int num_local_experts, int hidden, int proj,
+                         void* ws, size_t ws_bytes) {
+  DIHIP_REQUIRE(num_tokens >= 0 && top_k > 0 && hidden > 0 && proj > 0 && num_local_experts > 0 && num_local_experts <= 256,
+                DIHIP_PARAM_ERROR, "moe_sort_slots: bad shape (0 < num_local_experts <= 256)");
+  DIHIP_REQUIRE(experts, DIHIP_PARAM_ERROR, "moe_sort_slots: null pointer");
+  if (num_tokens == 0) return DIHIP_SUCCESS;
+  const size_t slots = (size_t)num_tokens * top_k;
+  DIHIP_REQUIRE(slots <= MOE_GEMM_MAX_SLOTS, DIHIP_EXCEED_LIMIT_ERROR, "moe_sort_slots: %zu (token, expert) slots exceed %zu", slots,
+                MOE_GEMM_MAX_SLOTS);
+  const size_t need = dihip_moe_gemm_workspace_bytes(num_tokens, top_k, num_local_experts, hidden, proj);
+  DIHIP_REQUIRE(ws && ws_bytes >= need, DIHIP_MEMORY_ERROR, "moe_sort_slots: workspace too small (%zu < %zu)", ws_bytes, need);
+  const MoeSortWs t = moe_sort_layout(reinterpret_cast<char*>(ws) + moe_sort_base(num_tokens, top_k, hidden, proj), slots, num_local_experts);
+  launch_moe_sort(reinterpret_cast<hipStream_t>(stream), t, experts, slots, num_local_experts);
+  return launch_status();
+}
+
+int dihip_moe_experts_gemm(void* stream, int wbits, const void* x, const int32_t* experts, const float* scores,
+                           const void* gate_packed, const void* gate_sz, const void* up_packed, const void* up_sz,
+                           const void* down_packed, const void* down_sz, int num_tokens, int top_k, int num_local_experts, int hidden,
+                           int proj, int group_size, void* out, void* ws, size_t ws_bytes, int dtype, int flags) {
+  const bool no_finalize = flags & DIHIP_MOE_NO_FINALIZE;
+  DIHIP_REQUIRE(wbits == 4 || wbits == 8, DIHIP_PARAM_ERROR, "moe_experts_gemm: wbits must be 4 or 8");
+  DIHIP_REQUIRE(dtype == DIHIP_BF16, DIHIP_PARAM_ERROR, "moe_experts_gemm: bf16 activations only");
+  DIHIP_REQUIRE((flags & ~DIHIP_MOE_NO_FINALIZE) == 0, DIHIP_PARAM_ERROR, "moe_experts_gemm: flags 0x%x (DIHIP_MOE_NO_FINALIZE only)", flags);
+  DIHIP_REQUIRE(num_tokens >= 0 && top_k > 0 && hidden > 0 && proj > 0 && num_local_experts > 0 && num_local_experts <= 256,
+                DIHIP_PARAM_ERROR, "moe_experts_gemm: bad shape (0 < num_local_experts <= 256)");
+  const int ktile = wbits == 4 ? 128 : 64;
+  DIHIP_REQUIRE(hidden % ktile == 0 && proj % ktile == 0 && (group_size <= 0 || group_size % ktile == 0), DIHIP_PARAM_ERROR,
+                "moe_experts_gemm: hidden = %d, proj = %d must be multiples of the k-tile (%d) and groups whole k-tiles", hidden, proj, ktile);
+  DIHIP_REQUIRE(x && experts && scores && gate_packed && gate_sz && up_packed && up_sz && down_packed && down_sz && (out || no_finalize),
+                DIHIP_PARAM_ERROR, "moe_experts_gemm: null pointer");
+  if (num_tokens == 0) return DIHIP_SUCCESS;
+  const size_t slots = (size_t)num_tokens * top_k;
+  DIHIP_REQUIRE(slots <= MOE_GEMM_MAX_SLOTS, DIHIP_EXCEED_LIMIT_ERROR, "moe_experts_gemm: %zu (token, expert) slots exceed %zu", slots,
+                MOE_GEMM_MAX_SLOTS);
+  const size_t need = dihip_moe_gemm_workspace_bytes(num_tokens, top_k, num_local_experts, hidden, proj);
+  DIHIP_REQUIRE(ws && ws_bytes >= need, DIHIP_MEMORY_ERROR, "moe_experts_gemm: workspace too small (%zu < %zu)", ws_bytes, need);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const MoeWs w = moe_ws_layout(ws, slots, hidden, proj);
+  const MoeSortWs t = moe_sort_layout(reinterpret_cast<char*>(ws) + moe_sort_base(num_tokens, top_k, hidden, proj), slots, num_local_experts);
+  launch_moe_sort(s, t, experts, slots, num_local_experts);
+  // gate/up: slot s reads row s / top_k of x;  down: its own row of the SwiGLU activations.  Both write row s (slot order)
+  int st = run_prefill_grouped(s, wbits, MOE_EPI_SWIGLU, x, hidden, top_k, gate_packed, gate_sz, up_packed, up_sz, w.act, proj, hidden,
+                               group_size, t.tiles, t.ntiles, t.sorted_slot, t.max_tiles);
+  if (st) return st;
+  st = run_prefill_grouped(s, wbits, MOE_EPI_STD, w.act, proj, 1, down_packed, down_sz, nullptr, nullptr, w.ys, hidden, proj, group_size,
+                           t.tiles, t.ntiles, t.sorted_slot, t.max_tiles);
+  if (st) return st;
+  if (no_finalize) return launch_status();  // dihip_moe_combine sums the slots
+  for (int t0 = 0; t0 < num_tokens; t0 += 65535) {  // the token is gridDim.y
+    const size_t s0 = (size_t)t0 * top_k;
+    hipLaunchKernelGGL(moe_finalize_kernel<DIHIP_BF16>, dim3((hidden + 511) / 512, std::min(num_tokens - t0, 65535)), dim3(256), 0, s,
+                       reinterpret_cast<char*>(out) + (size_t)t0 * hidden * 2, w.ys + s0 * hidden * 2, scores + s0, experts + s0, top_k, hidden);
+  }
+  return launch_status();
+}
+
 int dihip_moe_combine(void* stream, float* h_out, const float* h_res, const void* ws, const float* scores, const int32_t* experts,
                       const void* shared_out, const void* shared_gate, int num_tokens, int top_k, int hidden, int proj, int dtype) {
   DIHIP_REQUIRE(num_tokens >= 0 && top_k > 0 && hidden > 0 && proj > 0, DIHIP_PARAM_ERROR, "moe_combine: bad shape");
@@ -471,8 +652,12 @@ int dihip_moe_combine(void* stream, float* h_out, const float* h_res, const void
   if (num_tokens == 0) return DIHIP_SUCCESS;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const MoeWs w = moe_ws_layout(const_cast<void*>(ws), (size_t)num_tokens * top_k, hidden, proj);
-  hipLaunchKernelGGL(moe_combine_kernel<DIHIP_BF16>, dim3((hidden + 255) / 256, num_tokens), dim3(256), 0, s, h_out, h_res, w.ys, scores,
-                     experts, shared_out, shared_gate, top_k, hidden);
+  for (int t0 = 0; t0 < num_tokens; t0 += 65535) {  // the token is gridDim.y (one launch up to 65535 tokens, as before)
+    const size_t s0 = (size_t)t0 * top_k, h0 = (size_t)t0 * hidden;
+    hipLaunchKernelGGL(moe_combine_kernel<DIHIP_BF16>, dim3((hidden + 255) / 256, std::min(num_tokens - t0, 65535)), dim3(256), 0, s, h_out + h0,
+                       h_res ? h_res + h0 : nullptr, w.ys + s0 * hidden * 2, scores + s0, experts + s0,
+                       reinterpret_cast<const char*>(shared_out) + h0 * 2, reinterpret_cast<const char*>(shared_gate) + (size_t)t0 * 2, top_k, hidden);
+  }
   return launch_status();
 }
 

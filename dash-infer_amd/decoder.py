@@ -550,7 +550,10 @@ class DecodeSession:
                                  if 4 < batch <= 32 and i_loc % 32 == 0 and os.environ.get("DIHIP_MOE_ACT_FRAG", "1") != "0" else None)
             self.moe_shared = torch.empty(batch, cfg.hidden, dtype=dt, device=device)
             self.moe_sig = torch.empty(batch, 1, dtype=dt, device=device)
-            self.moe_ws = torch.empty(int(lib().dihip_moe_workspace_bytes(batch, mc.top_k, cfg.hidden, mc.moe_inter)), dtype=torch.uint8, device=device)
+            ws_bytes = int(lib().dihip_moe_workspace_bytes(batch, mc.top_k, cfg.hidden, mc.moe_inter))
+            if batch * mc.top_k > ops.MOE_GROUP_MAX_SLOTS:   # _moe_block: the grouped expert GEMM serves such a batch
+                ws_bytes = ops.moe_gemm_workspace_bytes(batch, mc.top_k, model.layers[0].exp_gate.num_experts, cfg.hidden, mc.moe_inter)
+            self.moe_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
             self.moe_dense_scratch = ops.Scratch(int(lib().dihip_dense_workspace_bytes(batch, mc.num_experts, cfg.hidden)), device)
         self.attn_frag = False  # set below: the op-boundary attention can write the o-projection's fragment layout
         # the SwiGLU output only feeds the down projection: when both run on the small-batch kernel it is
@@ -728,15 +731,22 @@ class DecodeSession:
         T, proj = h.shape[0], lw.exp_gate.N
         xn = ops.rmsnorm_rows(h, lw.ln2, cfg.eps)
         logits, sig = ops.moe_router_gate(xn, lw.router, lw.shared_sig)
-        ws = torch.empty(int(lib().dihip_moe_workspace_bytes(T, mc.top_k, cfg.hidden, mc.moe_inter)), dtype=torch.uint8, device=h.device)
+        # more slots than the grouped decode form serves: the context-phase grouped expert GEMM (DihipMoeBlockOp takes the same route)
+        gemm = T * mc.top_k > ops.MOE_GROUP_MAX_SLOTS
+        nbytes = (ops.moe_gemm_workspace_bytes(T, mc.top_k, lw.exp_gate.num_experts, cfg.hidden, proj) if gemm
+                  else int(lib().dihip_moe_workspace_bytes(T, mc.top_k, cfg.hidden, mc.moe_inter)))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=h.device)
         grouped = T > 1 and T * mc.top_k <= ops.MOE_GROUP_MAX_SLOTS and os.environ.get("DIHIP_MOE_FUSED", "1") != "0"
         if grouped:
             scores, experts = ops.moe_route_grouped(logits, mc.top_k, cfg.hidden, proj, ws, ep=lw.ep)
         else:
             scores, experts = ops.moe_route(logits, mc.top_k, ep=lw.ep)
-        out = ops.moe_experts(xn, experts, scores, lw.exp_gate, lw.exp_up, lw.exp_down, ws=ws,
-                              out=torch.empty(T, cfg.hidden, dtype=xn.dtype, device=h.device),
-                              flags=(ops.MOE_PREGROUPED | ops.MOE_NO_FINALIZE) if grouped else 0)
+        if gemm:
+            out = ops.moe_experts_gemm(xn, experts, scores, lw.exp_gate, lw.exp_up, lw.exp_down, ws=ws)
+        else:
+            out = ops.moe_experts(xn, experts, scores, lw.exp_gate, lw.exp_up, lw.exp_down, ws=ws,
+                                  out=torch.empty(T, cfg.hidden, dtype=xn.dtype, device=h.device),
+                                  flags=(ops.MOE_PREGROUPED | ops.MOE_NO_FINALIZE) if grouped else 0)
         act = ops.prenorm_swiglu(xn, lw.gate, lw.up, sc, T)
         shared = ops.gemm_lowp(act, lw.down, scratch=sc)
         if grouped:
@@ -896,8 +906,12 @@ class DecodeSession:
             ops.moe_route(self.moe_logits, cfg.moe.top_k, ep=lw.ep, scores=self.moe_scores, experts=self.moe_experts)
         if getattr(self, "_expert_log", None) is not None:
             self._expert_log.append(self.moe_experts.clone())
-        ops.moe_experts(self.moe_xn, self.moe_experts, self.moe_scores, lw.exp_gate, lw.exp_up, lw.exp_down, ws=self.moe_ws, out=self.moe_out,
-                        flags=(ops.MOE_PREGROUPED | ops.MOE_NO_FINALIZE) if fused else 0)
+        if B * cfg.moe.top_k > ops.MOE_GROUP_MAX_SLOTS:   # beyond the grouped decode form: the grouped expert GEMM (as DihipMoeBlockOp)
+            ops.moe_experts_gemm(self.moe_xn, self.moe_experts, self.moe_scores, lw.exp_gate, lw.exp_up, lw.exp_down, ws=self.moe_ws,
+                                 out=self.moe_out)
+        else:
+            ops.moe_experts(self.moe_xn, self.moe_experts, self.moe_scores, lw.exp_gate, lw.exp_up, lw.exp_down, ws=self.moe_ws,
+                            out=self.moe_out, flags=(ops.MOE_PREGROUPED | ops.MOE_NO_FINALIZE) if fused else 0)
         if self.moe_act_frag is not None:
             ops.prenorm_swiglu(self.moe_xn, lw.gate, lw.up, sc, B, out=self.moe_act_frag, y_layout=ops.ACT_FRAG32)
             ops.prenorm_gemm(self.moe_act_frag, lw.down, None, sc, B, x_layout=ops.ACT_FRAG32, out=self.moe_shared)

@@ -839,13 +839,16 @@ class DihipMoeBlockOp : public MoeA16W8HIP {
     static const bool fuse_on = env_on("DIHIP_MOE_FUSED", true), frag_on = env_on("DIHIP_MOE_ACT_FRAG", true);
     grouped_ = fuse_on && total_token_ > 1 && (int64_t)total_token_ * top_k_ <= 2048;  // decoder.DecodeSession._moe_block
     act_frag_ = frag_on && rt && !rt->is_context && total_token_ > 4 && total_token_ <= 32 && sg_.n % 32 == 0;
+    gemm_route_ = (int64_t)total_token_ * top_k_ > 2048;  // a prompt's rows: the grouped expert GEMM (decoder.DecodeSession._moe_rows)
+    const int64_t moe_ws_bytes = gemm_route_ ? (int64_t)dihip_moe_gemm_workspace_bytes(t, top_k_, ep_num_, hidden_, proj_)
+                                             : (int64_t)dihip_moe_workspace_bytes(t, top_k_, hidden_, proj_);
     // scratch rows shared by the layers' blocks (one block runs at a time)
     struct Need { const char* name; DataType dt; int64_t count; AsTensor** slot; };
     const size_t act_bytes = act_frag_ ? dihip_act_frag_bytes(total_token_, sg_.n) : (size_t)t * sg_.n * 2;
     const Need needs[] = {{"dihip.moe_xn", ftype_, (int64_t)t * hidden_, &xn_},      {"dihip.moe_logits", ftype_, (int64_t)t * num_expert_, &logits_},
                           {"dihip.moe_sig", ftype_, (int64_t)t, &sigv_},              {"dihip.moe_scores", FLOAT32, (int64_t)t * top_k_, &scores_},
                           {"dihip.moe_experts", INT32, (int64_t)t * top_k_, &idx_},   {"dihip.moe_out", ftype_, (int64_t)t * hidden_, &moe_out_},
-                          {"dihip.moe_shared", ftype_, (int64_t)t * hidden_, &shared_}, {"dihip.moe_ws", INT8, (int64_t)dihip_moe_workspace_bytes(t, top_k_, hidden_, proj_), &mws_}};
+                          {"dihip.moe_shared", ftype_, (int64_t)t * hidden_, &shared_}, {"dihip.moe_ws", INT8, moe_ws_bytes, &mws_}};
     for (const Need& n : needs) {
       auto it = tensor_map_->find(n.name);
       if (it == tensor_map_->end()) it = tensor_map_->emplace(n.name, std::make_shared<AsTensor>(n.name, DeviceType::HIP, n.dt, Shape{n.count})).first;
@@ -885,10 +888,16 @@ class DihipMoeBlockOp : public MoeA16W8HIP {
     } else {
       AS_CHECK_STATUS(FromDihip(dihip_moe_route_ep(s, logits_->GetDataPtr(), T, num_expert_, top_k_, scores, idx, dt, ep_first_, ep_num_)));
     }
-    AS_CHECK_STATUS(FromDihip(dihip_moe_experts_ex(s, 8, xn_->GetDataPtr(), idx, scores, gate_w_->GetDataPtr(), gate_sz_->GetDataPtr(), up_w_->GetDataPtr(),
-                                                   up_sz_->GetDataPtr(), down_w_->GetDataPtr(), down_sz_->GetDataPtr(), T, top_k_, hidden_, proj_,
-                                                   group_size_, moe_out_->GetDataPtr(), mws_->GetDataPtr(), mws_->GetSizeInByte(), dt,
-                                                   grouped_ ? (DIHIP_MOE_PREGROUPED | DIHIP_MOE_NO_FINALIZE) : 0)));
+    if (gemm_route_) {
+      AS_CHECK_STATUS(FromDihip(dihip_moe_experts_gemm(s, 8, xn_->GetDataPtr(), idx, scores, gate_w_->GetDataPtr(), gate_sz_->GetDataPtr(), up_w_->GetDataPtr(),
+                                                       up_sz_->GetDataPtr(), down_w_->GetDataPtr(), down_sz_->GetDataPtr(), T, top_k_, ep_num_, hidden_, proj_,
+                                                       group_size_, moe_out_->GetDataPtr(), mws_->GetDataPtr(), mws_->GetSizeInByte(), dt, 0)));
+    } else {
+      AS_CHECK_STATUS(FromDihip(dihip_moe_experts_ex(s, 8, xn_->GetDataPtr(), idx, scores, gate_w_->GetDataPtr(), gate_sz_->GetDataPtr(), up_w_->GetDataPtr(),
+                                                     up_sz_->GetDataPtr(), down_w_->GetDataPtr(), down_sz_->GetDataPtr(), T, top_k_, hidden_, proj_,
+                                                     group_size_, moe_out_->GetDataPtr(), mws_->GetDataPtr(), mws_->GetSizeInByte(), dt,
+                                                     grouped_ ? (DIHIP_MOE_PREGROUPED | DIHIP_MOE_NO_FINALIZE) : 0)));
+    }
     const int lay = act_frag_ ? DIHIP_ACT_FRAG32 : DIHIP_ACT_ROWMAJOR;
     AS_CHECK_STATUS(FromDihip(dihip_prenorm_swiglu(s, sg_.wbits, xn_->GetDataPtr(), DIHIP_ACT_ROWMAJOR, sg_.w->GetDataPtr(), sg_.sz->GetDataPtr(),
                                                    su_.w->GetDataPtr(), su_.sz->GetDataPtr(), act_->GetDataPtr(), T, sg_.n, sg_.k, sg_.group,

@@ -134,7 +134,10 @@ class MoeA16W8HIP : public AsOperator {
       topk_indice_ = std::make_unique<AsTensor>(op_name_ + ".topk_indice", DeviceType::HIP, INT32, Shape{slots});
       if (!experts_score_->GetDataPtr() || !topk_indice_->GetDataPtr()) return AsStatus::ALLSPARK_MEMORY_ERROR;
     }
-    const int64_t ws = (int64_t)dihip_moe_workspace_bytes(std::max(total_token_, 1), top_k_, hidden_, proj_);
+    // a prompt's rows (more slots than the grouped decode form serves): the grouped expert GEMM and its sort tables
+    gemm_route_ = (int64_t)total_token_ * top_k_ > 2048;
+    const int64_t ws = gemm_route_ ? (int64_t)dihip_moe_gemm_workspace_bytes(total_token_, top_k_, ep_num_, hidden_, proj_)
+                                   : (int64_t)dihip_moe_workspace_bytes(std::max(total_token_, 1), top_k_, hidden_, proj_);
     AsTensor* wsp = tensor_map_->at("workspace").get();  // shared scratch, grows only (model.cpp:241-243)
     if (wsp->GetSizeInByte() < (size_t)ws) AS_CHECK_STATUS(wsp->SetShape(Shape{ws}));
     return AsStatus::ALLSPARK_SUCCESS;
@@ -158,6 +161,11 @@ class MoeA16W8HIP : public AsOperator {
       AS_CHECK_STATUS(FromDihip(dihip_moe_route_ep(s, lg->GetDataPtr(), total_token_, num_expert_, top_k_, (float*)experts_score_->GetDataPtr(),
                                                    (int32_t*)topk_indice_->GetDataPtr(), DihipDtype(lg->GetDataType()), ep_first_, ep_num_)));
     }
+    if (gemm_route_)  // context phase: slots sorted by expert, one grouped MFMA GEMM per projection
+      return FromDihip(dihip_moe_experts_gemm(s, 8, x->GetDataPtr(), (const int32_t*)topk_indice_->GetDataPtr(), (const float*)experts_score_->GetDataPtr(),
+                                              gate_w_->GetDataPtr(), gate_sz_->GetDataPtr(), up_w_->GetDataPtr(), up_sz_->GetDataPtr(),
+                                              down_w_->GetDataPtr(), down_sz_->GetDataPtr(), total_token_, top_k_, ep_num_, hidden_, proj_,
+                                              group_size_, y->GetDataPtr(), wsp->GetDataPtr(), wsp->GetSizeInByte(), DihipDtype(ftype_), 0));
     return FromDihip(dihip_moe_experts_ex(s, 8, x->GetDataPtr(), (const int32_t*)topk_indice_->GetDataPtr(), (const float*)experts_score_->GetDataPtr(),
                                           gate_w_->GetDataPtr(), gate_sz_->GetDataPtr(), up_w_->GetDataPtr(), up_sz_->GetDataPtr(),
                                           down_w_->GetDataPtr(), down_sz_->GetDataPtr(), total_token_, top_k_, hidden_, proj_, group_size_,
@@ -167,6 +175,7 @@ class MoeA16W8HIP : public AsOperator {
 
  protected:
   int num_expert_ = 0, top_k_ = 0, hidden_ = 0, proj_ = 0, group_size_ = -1, total_token_ = 0, ep_num_ = 0, ep_first_ = 0;
+  bool gemm_route_ = false;  // Reshape: total_token_ * top_k_ > 2048 -> dihip_moe_experts_gemm
   DataType ftype_ = BFLOAT16;
   std::unique_ptr<AsTensor> gate_w_, up_w_, down_w_, gate_sz_, up_sz_, down_sz_, experts_score_, topk_indice_;
 };

@@ -282,6 +282,47 @@ def moe_experts(x, experts, scores, gate, up, down, ws=None, out=None, flags=0):
     return out
 
 
+MOE_GEMM_MAX_SLOTS = 1 << 20
+MOE_TILE_ROWS = 128
+
+
+def moe_gemm_workspace_bytes(T, top_k, num_experts, hidden, proj):
+    return int(lib().dihip_moe_gemm_workspace_bytes(T, top_k, num_experts, hidden, proj))
+
+
+def moe_experts_gemm(x, experts, scores, gate, up, down, ws=None, out=None, flags=0):
+    """moe_experts for the context phase (a prompt's rows): slots sorted by expert, one grouped MFMA GEMM per projection.  Any
+    T >= 1, T * top_k <= MOE_GEMM_MAX_SLOTS; flags: MOE_NO_FINALIZE.  `ws`: moe_gemm_workspace_bytes (the slot outputs lie where
+    moe_experts leaves them, so moe_combine follows unchanged)."""
+    T, hidden = x.shape
+    top_k = experts.shape[1]
+    proj, E = gate.N, gate.num_experts
+    ws = ws if ws is not None else torch.empty(moe_gemm_workspace_bytes(T, top_k, E, hidden, proj), dtype=torch.uint8, device=x.device)
+    if not flags & MOE_NO_FINALIZE:
+        out = out if out is not None else torch.empty(T, hidden, dtype=x.dtype, device=x.device)
+    check(lib().dihip_moe_experts_gemm(cur_stream(), gate.wbits, ptr(x), ptr(experts), ptr(scores), ptr(gate.w), ptr(gate.sz), ptr(up.w),
+                                       ptr(up.sz), ptr(down.w), ptr(down.sz), T, top_k, E, hidden, proj, gate.group, ptr(out), ptr(ws),
+                                       ws.numel(), dt_code(x), int(flags)), "dihip_moe_experts_gemm")
+    return out
+
+
+def moe_sort_slots(experts, num_experts, hidden, proj, ws=None):
+    """The slot sort of moe_experts_gemm alone.  Returns (expert_offset [E + 1], sorted_slot [slots], tiles [max_tiles, 4] =
+    {expert, first sorted position, rows, 0}, ntiles [1]) as int32 views into `ws`; sorted_slot is meaningful up to
+    expert_offset[E], tiles up to ntiles."""
+    T, top_k = experts.shape
+    slots, E = T * top_k, num_experts
+    ws = ws if ws is not None else torch.empty(moe_gemm_workspace_bytes(T, top_k, E, hidden, proj), dtype=torch.uint8, device=experts.device)
+    check(lib().dihip_moe_sort_slots(cur_stream(), ptr(experts), T, top_k, E, hidden, proj, ptr(ws), ws.numel()), "dihip_moe_sort_slots")
+    up = lambda v: (v + 255) // 256 * 256
+    base = up(int(lib().dihip_moe_workspace_bytes(T, top_k, hidden, proj)))
+    max_tiles = (slots + MOE_TILE_ROWS - 1) // MOE_TILE_ROWS + E
+    view = lambda off, n: ws[off:off + 4 * n].view(torch.int32)
+    o_sorted = base + up(4 * (E + 2))
+    o_tiles = o_sorted + up(4 * slots)
+    return view(base, E + 1), view(o_sorted, slots), view(o_tiles, 4 * max_tiles).view(max_tiles, 4), view(base + 4 * (E + 1), 1)
+
+
 def moe_route_grouped(logits, top_k, hidden, proj, ws, ep=None, scores=None, experts=None):
     """moe_route + the slot grouping of moe_experts in one launch (decode batches: 1 < T, T * top_k <= MOE_GROUP_MAX_SLOTS);
     follow with moe_experts(..., ws=ws, flags=MOE_PREGROUPED)."""

@@ -258,7 +258,8 @@ int dihip_a8w8_gemm_addto(void* stream, const void* x, const void* w_packed, con
                           const float* h_res, float* h_out, int M, int N, int K, void* ws, size_t ws_bytes, int dtype);
 
 /* ---------------------------------------------------------------------------------------------
- * 1b. Mixture-of-experts decode path with weight-only experts (BASELINE configs[4]).
+ * 1b. Mixture-of-experts block with weight-only experts (BASELINE configs[4]): the decode path
+ *     (one GEMV per slot / per group of <= 4 slots) and, below, the context phase (grouped GEMM on the MFMA).
  *     Semantics of the reference's MOE operator (csrc/core/operator/general/moe/moe_op.cpp:338-460): float
  *     softmax of the router logits, top-k WITHOUT renormalisation, per (token, expert) SiLU(x.Wgate) * (x.Wup)
  *     -> .Wdown, out[t] = sum_k score[t,k] * y[t,k] in float.  The reference's experts are bf16 / A8W8; these
@@ -309,6 +310,28 @@ int dihip_moe_experts_ex(void* stream, int wbits, const void* x, const int32_t* 
                          int group_size, void* out, void* ws, size_t ws_bytes, int dtype, int flags);
 int dihip_moe_combine(void* stream, float* h_out, const float* h_res, const void* ws, const float* scores, const int32_t* experts,
                       const void* shared_out, const void* shared_gate, int num_tokens, int top_k, int hidden, int proj, int dtype);
+/* The CONTEXT phase of the block (a prompt's rows): the expert GEMMs on the MFMA instead of one GEMV per slot.  The slots are
+ * sorted by expert (stable counting sort on the device, nothing read back), then ONE grouped launch of the context-phase GEMM per
+ * projection: a workgroup tile is <= 128 rows of one expert, gathered through the sort and scattered back, so the slot outputs
+ * lie where dihip_moe_experts_ex leaves them and dihip_moe_combine reads them unchanged.  A slot's result depends only on its own
+ * activation row and its expert's weights: it is the same bits however many other tokens share the call.  Not bit-identical to
+ * dihip_moe_experts (another summation order).  bf16; hidden and proj multiples of the k-tile (W8: 64, W4: 128).
+ *   dihip_moe_gemm_workspace_bytes : dihip_moe_workspace_bytes (same offsets) + the sort's tables; linear in the slot count
+ *   dihip_moe_sort_slots           : the tables alone, behind the block's workspace (256-byte aligned) as int32:
+ *                                    expert_offset [E + 1] | tile count [1] | pad to 256 B | sorted_slot [slots] (slot indices,
+ *                                    ascending inside an expert; slots with expert < 0 nowhere) | pad to 256 B |
+ *                                    tiles [ceil(slots / 128) + E][4] = {expert, first sorted position, rows <= 128, 0} | scratch
+ *   dihip_moe_experts_gemm         : sort + gate/up (SwiGLU) + down + finalize-routing; any num_tokens >= 1, at most
+ *                                    1 048 576 (token, expert) slots (DIHIP_EXCEED_LIMIT_ERROR above, before any launch);
+ *                                    flags: DIHIP_MOE_NO_FINALIZE as in dihip_moe_experts_ex.  No host synchronisation, no
+ *                                    allocation: the launches can be captured in a hipGraph. */
+size_t dihip_moe_gemm_workspace_bytes(int num_tokens, int top_k, int num_local_experts, int hidden, int proj);
+int dihip_moe_sort_slots(void* stream, const int32_t* experts, int num_tokens, int top_k, int num_local_experts, int hidden, int proj,
+                         void* ws, size_t ws_bytes);
+int dihip_moe_experts_gemm(void* stream, int wbits, const void* x, const int32_t* experts, const float* scores,
+                           const void* gate_packed, const void* gate_sz, const void* up_packed, const void* up_sz,
+                           const void* down_packed, const void* down_sz, int num_tokens, int top_k, int num_local_experts, int hidden,
+                           int proj, int group_size, void* out, void* ws, size_t ws_bytes, int dtype, int flags);
 /* The layer graph's two unquantised skinny Gemm operators on the normalised rows in one launch (qwen_v20_moe.py:330-338 "mlp.gate",
  * :360-365 "shared_expert_gate" with activation SIGMOID): router_logits FT [T, E] = FT(xn . W_router), shared_gate FT [T] =
  * FT(sigmoid(xn . w_gate)); both weights packed by dihip_dense_pack ([hidden, E] and [hidden, 1]). */
